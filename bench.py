@@ -19,11 +19,19 @@ the timed region: weak scaling; value = all ranks' speech tokens / max-over-rank
 (`python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...`) and fails loudly when the
 box has fewer than N GPUs; under an existing launcher (WORLD_SIZE set) it is one rank of that job.
 
-Prints ONE JSON line on rank 0.  Extra legs (rank 0, N = 1 only, outside the timed region):
+Prints ONE JSON line on rank 0.  A plain run does only what that line's headline figure needs: build the engines, warm up, time the
+`--steps` steps (`ms_per_step` = the milliseconds one timed step took), print.
+
+`--dump-outputs DIR` writes what the last timed step handed to its caller as `DIR/<name>.npy` (float32): `waveforms` (batch x samples,
+24 kHz), `waveform_lengths`, `codes` (batch x frames x codebooks).  Prompts, weights and sampling seeds are fixed by the arguments, so two
+builds of the library can be compared array for array.
+
+`--full` adds the extra legs (rank 0, N = 1 only, outside the timed region; each has its own `--no-...` switch):
   roofline      HIP-event timing of every launch of the dominant kernel (skinny weight-streaming GEMM) over one
                 eager generate call, against the 8 TB/s HBM peak
   cpu_baseline  the CPU oracle (oracle/*_ref.py: torch fp32 restatement of the reference) on a bounded sample of
                 the same workload, timed on this host's cores
+  parity_mode, configs, voice_clone_prompt, api_e2e: see the functions of those names below
 """
 import argparse
 import json
@@ -45,6 +53,36 @@ def log(msg):
 def synth_prompt(rng, cfg, lens, n_trail, scale=0.05):
     import synth
     return synth.rand_prompt(rng, cfg, lens, n_trail, scale)
+
+
+def synth_weights(tcfg, ccfg):
+    """`synth.talker_weights(tcfg, with_text=False)` and `synth.codec_weights(ccfg)`, the talker's tensors drawn on a thread pool: every
+    tensor has its own seeded generator (synth._rng), so values and order are those of the serial call (1.6 G values at 1.7B dims: most of a plain run's set-up time when drawn serially)."""
+    import synth
+    from concurrent.futures import ThreadPoolExecutor
+    shapes = synth.talker_param_shapes(tcfg, False)
+    with ThreadPoolExecutor(min(16, _host_threads())) as ex:
+        cw = ex.submit(synth.codec_weights, ccfg)
+        tw = dict(zip(shapes, ex.map(lambda kv: synth._talker_value(1234, kv[0], kv[1]), shapes.items())))
+        return tw, cw.result()
+
+
+DUMP_LIMIT_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(dirname, arrays):
+    """`--dump-outputs`: every entry of `arrays` (name -> tensor or array) as `dirname/<name>.npy` in float32, at most 64 MB in all.
+    An array over its share of that is cut to a fixed, seeded sample of its elements (flattened, ascending index)."""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    share = (DUMP_LIMIT_BYTES - 4096 * len(arrays)) // (4 * len(arrays))          # elements per array (4096: room for the .npy headers)
+    for name, a in arrays.items():
+        a = a.detach().float().cpu().numpy() if torch.is_tensor(a) else np.asarray(a, dtype=np.float32)
+        if a.size > share:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, share, replace=False))]
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a))
+    log(f"outputs written to {dirname}: " + ", ".join(arrays))
 
 
 def self_launch(n_gpus, argv, backend):
@@ -105,9 +143,18 @@ def main(argv=None, device=None):
                     help="metric = BASELINE.json's metric config (weak scaling: one batch per GPU); clone-shard = BASELINE "
                          "config 5, a FIXED job of --requests voice-clone requests dealt to the ranks (strong scaling)")
     ap.add_argument("--requests", type=int, default=256, help="clone-shard: requests in the job")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the extra legs (roofline, parity_mode, configs, voice_clone_prompt, api_e2e, cpu_baseline); "
+                         "a plain run measures the headline figure only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the arrays the last timed step returned to DIR/<name>.npy (float32; rank 0)")
     args = ap.parse_args(argv)
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if not args.full:                    # a plain run: no leg beyond the timed steps
+        args.no_roofline = args.no_parity_mode = args.no_configs = args.no_api_e2e = args.no_cpu_baseline = True
     if args.batch is None:
         args.batch = 32 if args.workload == "clone-shard" else 8
     if args.engines is None:
@@ -163,8 +210,7 @@ def main(argv=None, device=None):
         return
     B, F = args.batch, args.frames
     t0 = time.time()
-    tw_np = synth.talker_weights(tcfg, with_text=False)
-    cw_np = synth.codec_weights(ccfg)
+    tw_np, cw_np = synth_weights(tcfg, ccfg)
     td = lambda w: {k: torch.from_numpy(v) for k, v in w.items()}
     lens = [24 + 4 * (i % 8) + 12 for i in range(B)]          # 128-char prompts ~ 24..52 text tokens + 12 prefix rows
     talker = TalkerEngine(tcfg, td(tw_np), weight_dtype=torch.bfloat16 if args.talker_dtype == "bf16" else torch.float32, device=dev, max_batch=B,
@@ -262,6 +308,11 @@ def main(argv=None, device=None):
             assert bool(torch.isfinite(gw).all())
     assert all(int(x) == F * ccfg.total_upsample for x in wl)
     assert bool(torch.isfinite(wav).all())
+    if args.dump_outputs and rank == 0:            # what the last timed step returned: this rank's waveforms and, unless overlapped, its codes
+        dumped = {"waveforms": wav, "waveform_lengths": torch.as_tensor(wl)}
+        if out is not None:
+            dumped["codes"] = out.codes
+        dump_outputs(args.dump_outputs, dumped)
 
     G = tcfg.num_code_groups
     tokens_total = world * B * F * G * args.steps
@@ -466,6 +517,15 @@ def clone_shard_job(args, tcfg, ccfg, dev, rank, world, dist, weights=None, keep
         return None
     assert all(allw[i] is not None and allw[i].shape[0] == frames[i] * ccfg.total_upsample for i in range(NREQ))
     assert all(bool(torch.isfinite(allw[i]).all()) for i in range(0, NREQ, max(1, NREQ // 16)))
+    if args.dump_outputs:                  # the last job's waveforms: a fixed, seeded choice of whole requests, 16 MB at the most
+        picked, room = [], DUMP_LIMIT_BYTES // 16
+        for i in np.random.default_rng(0).permutation(NREQ).tolist():
+            if allw[i].numel() <= room:
+                picked.append(i)
+                room -= allw[i].numel()
+        picked.sort()
+        dump_outputs(args.dump_outputs, {"waveforms": torch.cat([allw[i] for i in picked]), "waveform_requests": picked,
+                                         "waveform_lengths": [allw[i].numel() for i in range(NREQ)]})
     G = tcfg.num_code_groups
     tok = sum(frames) * G * args.steps
     audio_s = sum(frames) * ccfg.total_upsample / 24000.0 * args.steps
@@ -582,6 +642,7 @@ def configs_leg(args, tcfg, ccfg, tw_np, cw_np, dev):
     # ---- config 5 at N = 1 (its engines, batch 32, serve config 4 too)
     a5 = _ap.Namespace(**vars(args))
     a5.requests, a5.batch, a5.engines, a5.steps, a5.warmup, a5.workload = (6, 2, 2, 1, 1, "clone-shard") if small else (256, 32, 2, 1, 1, "clone-shard")
+    a5.dump_outputs = None                 # (the dump belongs to the timed steps of the run, not to this leg)
     keep = {}
     r5 = clone_shard_job(a5, tcfg, ccfg, dev, 0, 1, None, weights=(tw_np, cw_np), keep=keep)
     wb17 = keep["talkers"][0].stats()["weight_bytes_per_frame"]

@@ -12,6 +12,31 @@ GOLDEN = os.path.join(ROOT, "tests", "golden")
 # os.environ inside the process: the library looks at the environment once per switch.
 
 
+def _cpu_workers():
+    try:
+        n = len(os.sched_getaffinity(0))
+    except AttributeError:
+        n = os.cpu_count() or 1
+    return max(1, min(n - 1, 8))
+
+
+@pytest.hookimpl(tryfirst=True)
+def pytest_cmdline_main(config):
+    """The CPU suite (`-m "not gpu"`) is bound by the single-threaded SIMT emulator: about two and a half hours of independent tests in one
+    process.  Where pytest-xdist is installed and the command line says nothing about workers, that selection runs on worker processes
+    (the cores this process may use less one, 8 at the most).  Any other selection -- the GPU tests above all -- stays in one process."""
+    opt = config.option
+    if "not gpu" not in (getattr(opt, "markexpr", "") or "") or not config.pluginmanager.hasplugin("xdist"):
+        return None
+    if getattr(opt, "numprocesses", None) is not None or getattr(opt, "dist", "no") != "no" or getattr(opt, "tx", None) \
+            or getattr(opt, "collectonly", False) or getattr(opt, "usepdb", False) or os.environ.get("PYTEST_XDIST_WORKER"):
+        return None
+    n = _cpu_workers()
+    if n > 1:
+        opt.numprocesses = n
+    return None
+
+
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run with `-m gpu` on the GPU box)")
 

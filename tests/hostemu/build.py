@@ -12,6 +12,7 @@ import hashlib
 import os
 import re
 import subprocess
+from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
@@ -50,6 +51,15 @@ def _compiler():
             return c
 
 
+def _jobs():
+    """Compiler processes at a time: the cores this process may use, 8 at the most."""
+    try:
+        n = len(os.sched_getaffinity(0))
+    except AttributeError:
+        n = os.cpu_count() or 1
+    return max(1, min(n, 8))
+
+
 def _transform(src_path, dst_path):
     s = open(src_path).read()
     s = s.replace("extern __shared__", "extern")
@@ -59,6 +69,15 @@ def _transform(src_path, dst_path):
 
 
 def build(verbose=False):
+    """Returns the library's path; builds it first when an input changed.  One builder at a time (the test workers of a parallel
+    run all ask for it at once): the others wait on the lock file and then find the stamp in place."""
+    import fcntl
+    with open(OUT + ".lock", "w") as lock:
+        fcntl.flock(lock, fcntl.LOCK_EX)
+        return _build(verbose)
+
+
+def _build(verbose):
     inputs = [os.path.join(CSRC, f) for f in ENGINES + SIMT_KERNELS] + [os.path.join(HERE, f) for f in STANDIN] + HEADERS + [__file__]
     h = hashlib.sha256()
     for f in inputs:
@@ -81,14 +100,15 @@ def build(verbose=False):
         _transform(os.path.join(CSRC, f), dst)
         objs.append((dst, (["-DQTTS_SIMT_SEQUENTIAL"] if f in SEQUENTIAL else []) + EXTRA_DEFS.get(f, [])))
     objs += [(os.path.join(HERE, f), []) for f in STANDIN]
-    outs = []
+    outs, cmds = [], []
     for src, extra in objs:
         o = os.path.join(GEN, os.path.basename(src) + ".o")
-        cmd = base + extra + ["-c", src, "-o", o]
+        cmds.append(base + extra + ["-c", src, "-o", o])
         if verbose:
-            print(" ".join(cmd))
-        subprocess.run(cmd, check=True)
+            print(" ".join(cmds[-1]))
         outs.append(o)
+    with ThreadPoolExecutor(_jobs()) as ex:           # the translation units are independent: compile them side by side
+        list(ex.map(lambda cmd: subprocess.run(cmd, check=True), cmds))
     subprocess.run([cc, "-shared", "-o", OUT] + san + outs, check=True)
     with open(stamp, "w") as fh:
         fh.write(h.hexdigest())

@@ -1,7 +1,7 @@
 """TEST INFRASTRUCTURE: dump the tokens sampling.hip draws on the emulator for a fixed set of logits / processor settings /
 Philox keys (ties, an all-equal row that overflows the candidate buffer, repetition penalty, top-p, blocked EOS).  Run once
-plain and once with QTTS_HOSTEMU_DEFS=-DQTTS_SAMPLER_V2=1: the two dumps must be identical (tests/test_hostemu.py,
-QTTS_TEST_VARIANTS=1).  Usage: python tests/hostemu/variant_probe.py out.npy"""
+plain and once with QTTS_HOSTEMU_DEFS=-DQTTS_SAMPLER_V2=1: the two dumps must be identical (tests/test_hostemu.py:
+test_build_variants_agree_with_default_on_emulator).  Usage: python tests/hostemu/variant_probe.py out.npy"""
 import sys, os, ctypes as C, numpy as np
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import build as hb

@@ -136,18 +136,40 @@ def test_bench_self_launches_two_ranks_gloo_on_the_emulator():
 def test_bench_api_e2e_leg_on_the_emulator():
     """bench.py's `api_e2e` leg (round 4): `Qwen3TTSModel.generate_custom_voice` from Python strings to host numpy waveforms, timed
     end to end next to the S2 step, with the parts the S2 step does not contain itemised.  Here: tiny dims on the emulator."""
-    j = _bench_on_emulator("--gpus", "1", "--model", "tiny", "--batch", "2", "--frames", "3", "--steps", "1", "--warmup", "0",
+    j = _bench_on_emulator("--gpus", "1", "--model", "tiny", "--batch", "2", "--frames", "3", "--steps", "1", "--warmup", "0", "--full",
                            "--no-roofline", "--no-cpu-baseline", "--no-parity-mode", "--no-configs", "--talker-dtype", "f32", "--codec-dtype", "f32")
     a = j["api_e2e"]
     assert "INVALID" in j and a["calls"] >= 1 and a["ms_per_call"] > 0 and a["frames_generated_per_row"] == 3
     assert 0 < a["frames_returned_mean"] <= 3 and set(a["not_in_s2_ms"]) and a["s2_ms_per_step"] == j["ms_per_step"]
 
 
+def test_bench_plain_run_has_no_extra_leg_and_dumps_its_outputs_on_the_emulator(tmp_path):
+    """A plain run (no `--full`) times its `--steps` steps and prints the line, nothing else; `--dump-outputs DIR` leaves what the last
+    timed step returned as float32 `.npy` files, identical from run to run for the same arguments."""
+    import synth
+    t, c = synth.talker_tiny(), synth.codec_tiny()
+    runs = []
+    for d in ("a", "b"):
+        j = _bench_on_emulator("--gpus", "1", "--model", "tiny", "--batch", "2", "--frames", "3", "--steps", "2", "--warmup", "0",
+                               "--talker-dtype", "f32", "--codec-dtype", "f32", "--dump-outputs", str(tmp_path / d))
+        assert not set(j) & {"roofline", "parity_mode", "configs", "voice_clone_prompt", "api_e2e", "cpu_baseline", "cpu_baseline_reference"}
+        assert j["steps"] == 2 and j["ms_per_step"] > 0 and j["unit"] == "speech-tokens/s" and j["higher_is_better"] is True and j["dtype"] == "f32"
+        assert abs(j["value"] - 2 * 3 * t.num_code_groups / (j["ms_per_step"] * 1e-3)) <= 0.01 * j["value"]
+        runs.append({f: np.load(tmp_path / d / f) for f in sorted(os.listdir(tmp_path / d))})
+    a, b = runs
+    assert sorted(a) == ["codes.npy", "waveform_lengths.npy", "waveforms.npy"]
+    assert all(v.dtype == np.float32 for v in a.values())
+    assert a["codes.npy"].shape == (2, 3, t.num_code_groups) and a["waveforms.npy"].shape == (2, 3 * c.total_upsample)
+    assert a["waveform_lengths.npy"].tolist() == [3 * c.total_upsample] * 2 and np.isfinite(a["waveforms.npy"]).all()
+    assert np.abs(a["waveforms.npy"]).max() > 0
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+
+
 def test_bench_configs_and_voice_clone_prompt_legs_on_the_emulator():
     """bench.py's `configs` leg (round 5: BASELINE configs 2-5 on the driver's line -- codec-only, the small model at batch 8, first packet
     at batch 32, the clone-shard job at N = 1) and its `voice_clone_prompt` leg (create_voice_clone_prompt through the real wrapper, the two
     encoders behind it), at test dims on the emulator: every sub-object is there, carries its numbers and its roofline denominator."""
-    j = _bench_on_emulator("--gpus", "1", "--model", "tiny", "--batch", "2", "--frames", "3", "--steps", "1", "--warmup", "0",
+    j = _bench_on_emulator("--gpus", "1", "--model", "tiny", "--batch", "2", "--frames", "3", "--steps", "1", "--warmup", "0", "--full",
                            "--no-roofline", "--no-cpu-baseline", "--no-parity-mode", "--no-api-e2e", "--talker-dtype", "f32", "--codec-dtype", "f32")
     c = j["configs"]
     assert "error" not in c, c

@@ -1846,7 +1846,6 @@ def test_prompt_assembly_orchestration_vs_reference_golden(emu, golden_dir):
         emu.qtts_talker_destroy(h)
 
 
-@pytest.mark.skipif(not FULL, reason="QTTS_HOSTEMU_FULL=1 (minutes on the emulator; the batch-32 case runs on the MI355X in tests/test_gpu_parity.py)")
 def test_talker_orchestration_large_ragged_batch_vs_oracle(emu):
     """Twenty ragged, left-padded prompts (M = 20 rows per decode step, 40 in the code predictor's two-token first pass,
     several KV pages per sequence) through the real talker C++ on CPU kernels, against the oracle's greedy run."""
@@ -2358,7 +2357,6 @@ def test_talker_bf16_prefill_bf16_handover_changes_nothing(emu, qopt):
     assert c1.shape[1] >= 1 and np.array_equal(c1, c0) and np.array_equal(k1, k0) and np.array_equal(h1, h0)
 
 
-@pytest.mark.skipif(not FULL, reason="QTTS_HOSTEMU_FULL=1 (2 min; a hardening pass of the emulator, not a parity gate)")
 def test_results_do_not_depend_on_wave_scheduling_order(emu, codec, golden_dir):
     """The hardware runs the waves of a workgroup in no particular order; the emulator's default is ascending thread id.
     Re-run the kernel-level cases, the encoder, the speaker encoder, a short decode (whole and streamed) and a short talker
@@ -2401,9 +2399,6 @@ def test_results_do_not_depend_on_wave_scheduling_order(emu, codec, golden_dir):
         emu.hostemu_set_fiber_order(0)
 
 
-@pytest.mark.skipif(os.environ.get("QTTS_TEST_VARIANTS") != "1",
-                    reason="the remaining A/B build variant (qwen3-tts_amd/build.py VARIANTS: attn_tail) on the emulator: one extra "
-                           "emulator build, ~10 min -- enable with QTTS_TEST_VARIANTS=1")
 def test_build_variants_agree_with_default_on_emulator(tmp_path):
     """attn_tail (KV beyond the 256-key window read 4 chunks per latency round), compiled into the emulated library with its -D
     flag (QTTS_HOSTEMU_DEFS): passes the decode-attention kernel test (long sequences included) and the talker goldens, and
@@ -2414,7 +2409,6 @@ def test_build_variants_agree_with_default_on_emulator(tmp_path):
     for defs, sel in (("", "bf16_small_batch"),
                       ("-DQTTS_ATTN_TAIL_BATCH=1", "attn_decode or talker_orchestration_greedy or bf16_small_batch")):
         env = dict(os.environ, QTTS_HOSTEMU_DEFS=defs, QTTS_PROBE_OUT=str(tmp_path / f"probe{len(probes)}.npy"))
-        env.pop("QTTS_TEST_VARIANTS", None)
         r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-x", "-q", "-k", sel], env=env,
                            capture_output=True, text=True)
         assert r.returncode == 0, (defs, r.stdout[-2000:])
