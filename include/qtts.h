@@ -47,8 +47,9 @@ const char* qtts_last_error(void);
  * 6: + qtts_talker_stream_*; 7: + qtts_talker_set_teacher; 8: + qtts_talker_set_profile / get_gemm_profile;
  * 9: + qtts_codec_get_stats; 10: + qtts_set_option / qtts_get_option, qtts_talker_stats grew the fused-launch fields;
  * 11: + qtts_talker_debug_cp_logits, qtts_talker_stats.cp_layer_per_step in the reserved word;
- * 12: + qtts_talker_stats.ks_split_per_step (appended)). */
-#define QTTS_ABI_VERSION 12
+ * 12: + qtts_talker_stats.ks_split_per_step (appended); 13: qtts_talker_stats.attn_gq_per_step in the reserved word, the talker
+ * engine takes head_dim 64 | 128 and GQA groups of 1..8). */
+#define QTTS_ABI_VERSION 13
 int qtts_abi_version(void);
 
 /* A/B switches of the library (measuring tools and tests; a deployment sets none).  Every switch has a name of the form
@@ -258,6 +259,10 @@ int qtts_speaker_embed(qtts_speaker* s, const float* wav_dev, int32_t B, int32_t
  * ------------------------------------------------------------------------------------------ */
 typedef struct qtts_talker qtts_talker;
 
+/* Supported head shapes, for the talker and the code predictor independently: head_dim 64 or 128, num_attention_heads a multiple of
+ * num_key_value_heads with a GQA group (heads / kv heads) of 1..8.  head_dim 128 with a group <= 2 (the released checkpoints) runs the
+ * specialised decode attentions and the code predictor's fused launches; every other shape the general decode attention
+ * (qtts_talker_stats.attn_gq_per_step).  Anything else is refused by finalize with QTTS_ERR_ARG. */
 typedef struct {
     /* Qwen3TTSTalkerConfig (configuration_qwen3_tts.py:370-454) */
     int32_t vocab_size;
@@ -406,7 +411,8 @@ typedef struct {
                                      * and cp_mlp_per_step too.  (ABI v11: the former reserved word.)                                        */
     int32_t ks_split_per_step;      /* decode GEMMs of that frame step that split K over workgroups and combine inside the launch (skinny.hip: skinny2_ks_kernel;
                                      * bf16 engines at batch 17..32: the o- / down-projections; ABI v12)                                       */
-    int32_t reserved0;
+    int32_t attn_gq_per_step;       /* decode-attention launches of that frame step that ran the general kernel family (attn_gq.h: any head shape beyond
+                                     * head_dim 128 with a group <= 2, or every launch under QTTS_ATTN_GQ=1; ABI v13: the former reserved word) */
 } qtts_talker_stats;
 int qtts_talker_get_stats(qtts_talker* t, qtts_talker_stats* out);
 /* Per-class result of the profile mode (qtts_talker_set_profile(t, 1), ABI v8): every launch of the decode GEMM in frames 1..6

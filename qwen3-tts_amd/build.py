@@ -22,7 +22,7 @@ SOURCES = ["gemm_tap.hip", "resunit.hip", "skinny.hip", "elementwise.hip", "atte
            "speaker_kernels.hip", "speaker_engine.hip", "stream_kernels.hip"]
 # sources that only a measuring variant links (never the product library): variant name -> files
 VARIANT_SOURCES = {"probe": ["persist_probe.hip"]}
-HEADERS = ["common.h", "kernels.h", "glue.h", "granule.h", "attn_helpers.h", "tstamp.h", os.path.join("..", "..", "include", "qtts.h")]
+HEADERS = ["common.h", "kernels.h", "glue.h", "granule.h", "attn_helpers.h", "attn_gq.h", "tstamp.h", os.path.join("..", "..", "include", "qtts.h")]
 # -amdgpu-kernarg-preload-count: the leading scalar kernel arguments (14 dwords on gfx950) arrive in user SGPRs with the wave instead
 # of behind an `s_load` round trip; the frame step's decode GEMMs (skinny8_kernel, skinny8_f32_kernel) pass their address operands that way.
 # The flag applies to every kernel of the library (only leading SCALAR arguments are ever preloaded; a kernel whose first argument is a

@@ -15,6 +15,7 @@
 #include "tstamp.h"
 #include "granule.h"
 #include "attn_helpers.h"
+#include "attn_gq.h"
 #include <hip/hip_ext.h>
 
 QTTS_TS_UNIT(attn)
@@ -1456,6 +1457,61 @@ void launch_rope_table(const float* inv_freq, int n_pos, float* out, hipStream_t
     QTTS_CHECK_HIP(hipGetLastError());
 }
 
+// =================================================================================== attn_gq (attn_gq.h): any group 1..8, head_dim 64 | 128
+// The __global__ wrappers own the LDS arrays; NC = column capacity (8 | 16 >= group * n_new).
+template <int HD, int NC, bool CT>
+__global__ __launch_bounds__(256) void attn_gq16_kernel(AttnDecodeParams p) {
+    __shared__ __attribute__((aligned(16))) float xs[(NC + 4) * HD];
+    __shared__ __attribute__((aligned(16))) float red[4 * NC * HD];
+    __shared__ float gm[4 * NC], gl[4 * NC], snew[2 * NC];
+    attn_gq16_body<HD, NC, CT>(p, xs, red, gm, gl, snew);
+}
+template <typename KVT, int HD, int NC, bool CT>
+__global__ __launch_bounds__(256) void attn_gqv_kernel(AttnDecodeParams p) {
+    __shared__ __attribute__((aligned(16))) float xs[(NC + 4) * HD];
+    __shared__ __attribute__((aligned(16))) float red[16 * HD];
+    __shared__ float gm[16], gl[16], snew[2 * NC];
+    attn_gqv_body<KVT, HD, NC, CT>(p, xs, red, gm, gl, snew);
+}
+template <int HD>
+__global__ __launch_bounds__(256) void attn_gq_merge_kernel(AttnDecodeParams p) { attn_gq_merge_body<HD>(p); }
+
+template <int HD, int NC>
+static void launch_attn_gq_k(const AttnDecodeParams& p, dim3 grid, hipStream_t st) {
+    if (p.kv.vt) {
+        if (p.kv.contig) hipLaunchKernelGGL((attn_gq16_kernel<HD, NC, true>), grid, dim3(256), 0, st, p);
+        else hipLaunchKernelGGL((attn_gq16_kernel<HD, NC, false>), grid, dim3(256), 0, st, p);
+    } else if (p.kv.bf16) {
+        if (p.kv.contig) hipLaunchKernelGGL((attn_gqv_kernel<bf16_t, HD, NC, true>), grid, dim3(256), 0, st, p);
+        else hipLaunchKernelGGL((attn_gqv_kernel<bf16_t, HD, NC, false>), grid, dim3(256), 0, st, p);
+    } else {
+        if (p.kv.contig) hipLaunchKernelGGL((attn_gqv_kernel<float, HD, NC, true>), grid, dim3(256), 0, st, p);
+        else hipLaunchKernelGGL((attn_gqv_kernel<float, HD, NC, false>), grid, dim3(256), 0, st, p);
+    }
+}
+bool attn_decode_uses_gq(const AttnDecodeParams& p) {
+    return p.force_gq || !(p.hd == 128 && p.nkv > 0 && p.nh / p.nkv <= 2);
+}
+static void launch_attn_gq(const AttnDecodeParams& p, hipStream_t st) {
+    QTTS_REQUIRE((p.hd == 64 || p.hd == 128) && p.kv.hd == p.hd, QTTS_ERR_ARG, "attn_decode: head_dim must be 64 or 128");
+    QTTS_REQUIRE(p.nkv >= 1 && p.nh % p.nkv == 0 && p.nh / p.nkv >= 1 && p.nh / p.nkv <= 8, QTTS_ERR_ARG,
+                 "attn_decode: 1..8 query heads per kv head (num_attention_heads a multiple of num_key_value_heads)");
+    QTTS_REQUIRE(p.n_new == 1 || p.n_new == 2, QTTS_ERR_ARG, "attn_decode: 1 or 2 new tokens");
+    QTTS_REQUIRE(!p.kv.vt || p.kv.bf16, QTTS_ERR_ARG, "attn_decode: transposed V pages are a bf16-cache layout");
+    const int NQ = p.n_new * (p.nh / p.nkv);
+    const int ns = p.nsplit > 1 ? p.nsplit : 1;
+    QTTS_REQUIRE(ns == 1 || (p.part && p.n_new == 1), QTTS_ERR_ARG, "attn_decode: split-KV needs the partial-result buffer and a single new token");
+    const dim3 grid(p.B * p.nkv, ns);
+    if (p.hd == 128) { if (NQ <= 8) launch_attn_gq_k<128, 8>(p, grid, st); else launch_attn_gq_k<128, 16>(p, grid, st); }
+    else { if (NQ <= 8) launch_attn_gq_k<64, 8>(p, grid, st); else launch_attn_gq_k<64, 16>(p, grid, st); }
+    if (ns > 1) {
+        if (p.hd == 128) hipLaunchKernelGGL((attn_gq_merge_kernel<128>), dim3(p.B * p.nkv), dim3(256), 0, st, p);
+        else hipLaunchKernelGGL((attn_gq_merge_kernel<64>), dim3(p.B * p.nkv), dim3(256), 0, st, p);
+    }
+    QTTS_CHECK_HIP(hipGetLastError());
+}
+
+
 template <typename KVT, int NQ, bool CT>
 static void launch_attn_decode_c(const AttnDecodeParams& p, size_t lds, hipStream_t st);
 template <typename KVT, int NQ>
@@ -1471,6 +1527,9 @@ static void launch_attn_decode_c(const AttnDecodeParams& p, size_t lds, hipStrea
 }
 
 void launch_attn_decode(const AttnDecodeParams& p, hipStream_t st) {
+    // head_dim 128 with a group <= 2 runs the five kernels above, exactly as before; every other shape (and, with QTTS_ATTN_GQ=1,
+    // every launch of an engine) the general family of attn_gq.h
+    if (attn_decode_uses_gq(p)) { launch_attn_gq(p, st); return; }
     QTTS_REQUIRE(p.hd == 128, QTTS_ERR_ARG, "attn_decode: head_dim must be 128");
     const int GQ = p.nh / p.nkv, NQ = p.n_new * GQ;
     QTTS_REQUIRE((NQ == 1 || NQ == 2 || NQ == 4) && p.n_new <= 2, QTTS_ERR_ARG, "attn_decode: 1, 2 or 4 queries per kv head");

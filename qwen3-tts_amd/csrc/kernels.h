@@ -223,16 +223,20 @@ struct AttnDecodeParams {
     int max_len;                 // LDS score capacity
     const int* done_flag;
     // split-KV (talker, long sequences): nsplit > 1 workgroups per (sequence, kv head), each over max_len / nsplit keys, partial
-    // results in `part` [B*nkv][nsplit][GQ][128 + 2] fp32 (numerator | max | denominator), merged by a second tiny kernel
+    // results in `part` [B*nkv][nsplit][GQ][hd + 2] fp32 (numerator | max | denominator), merged by a second tiny kernel
     int nsplit; float* part;
     // optional [rope_cs_n][2][64]: cos | sin of pos * inv_freq for positions < rope_cs_n, filled by launch_rope_table with the very
     // expression the kernels evaluate (bit-identical); attn_cp (static position, known at launch) requests its row at kernel entry
     // instead of running sinf / cosf behind the arrival of the qkv row
     const float* rope_cs; int rope_cs_n;
+    int force_gq;                // 1: the general family (attn_gq.h) also for head_dim 128 with a group <= 2 (QTTS_ATTN_GQ=1: A/B, goldens)
 };
 void launch_attn_decode(const AttnDecodeParams& p, hipStream_t st);
+// whether launch_attn_decode runs the general family (attn_gq.h: head_dim 64 | 128, group 1..8) for this call: every shape the older
+// kernels do not have (they keep head_dim 128 with a group <= 2), or force_gq
+bool attn_decode_uses_gq(const AttnDecodeParams& p);
 void launch_rope_table(const float* inv_freq, int n_pos, float* out, hipStream_t st);
-inline size_t attn_part_floats(int B, int nkv, int nsplit, int gq) { return (size_t)B * nkv * nsplit * gq * 130; }
+inline size_t attn_part_floats(int B, int nkv, int nsplit, int gq, int hd = 128) { return (size_t)B * nkv * nsplit * gq * (hd + 2); }
 
 // The code predictor's passes >= 1, attention + o-projection in one launch (attention.hip: cp_attn_o_kernel).  `a` as for
 // launch_attn_decode (its out / ldo / out_bf16 are not used); the o-projection's operator packed by pack_skinny_weight(bf16, fs = 16).

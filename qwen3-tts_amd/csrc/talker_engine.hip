@@ -60,6 +60,9 @@ struct qtts_talker {
 
     // KV caches
     DevBuf kpool_t, vpool_t, kpool_c, vpool_c, ptab_t, ptab_c, attn_part;
+    bool attn_gq_env = QTTS_OPT_SET("QTTS_ATTN_GQ");   // A/B: the general decode-attention family (attn_gq.h) for every launch, read at engine creation
+    int64_t attn_gq_count = 0;         // launches of that family ...
+    int attn_gq_per_step = 0;          // ... in the frame step last launched / captured
     int attn_nsplit = 1;               // talker decode attention: workgroups per (sequence, kv head); > 1 when max_seq > 512
     KvCache kv_t, kv_c;
     // decode state / scratch
@@ -366,7 +369,7 @@ struct qtts_talker {
         a.qw = L.qn.as<float>(); a.kw = L.kn.as<float>(); a.eps = d.eps; a.inv_freq = inv_freq; a.n_pad = npad;
         a.len_dev = len_dev; a.len_static = len_static; a.kv = kv; a.layer = layer; a.out = attb; a.ldo = d.qd;
         a.max_len = max_len; a.done_flag = ss.done;
-        a.rope_cs = rope_cs; a.rope_cs_n = rope_cs_n;
+        a.rope_cs = rope_cs; a.rope_cs_n = rope_cs_n; a.force_gq = attn_gq_env ? 1 : 0;
         if (len_dev && attn_nsplit_active > 1) {     // talker, long sequences: split-KV over the LIVE length's bucket, not the capacity
             a.nsplit = attn_nsplit_active; a.part = attn_part.as<float>(); a.max_len = attn_span_active;
         }
@@ -446,7 +449,7 @@ struct qtts_talker {
             } else launch_cp_attn_o(f, st);
             ++cp_attn_o_count;
         } else {
-        if (!skinny_only) launch_attn_decode(a, st);
+        if (!skinny_only) { launch_attn_decode(a, st); if (attn_decode_uses_gq(a)) ++attn_gq_count; }
         SkinnyParams o{};
         o.done_flag = ss.done;
         o.x_bf16 = att16;
@@ -671,8 +674,17 @@ void qtts_talker::finalize() {
           c.num_attention_heads * c.head_dim, c.num_key_value_heads * c.head_dim, c.rms_norm_eps};
     cd = {c.cp_hidden_size, c.cp_intermediate_size, c.cp_num_attention_heads, c.cp_num_key_value_heads, c.cp_head_dim,
           c.cp_num_attention_heads * c.cp_head_dim, c.cp_num_key_value_heads * c.cp_head_dim, c.cp_rms_norm_eps};
-    QTTS_REQUIRE(td.hd == 128 && cd.hd == 128, QTTS_ERR_ARG, "talker/code-predictor head_dim must be 128");
-    QTTS_REQUIRE(td.nh / td.nkv <= 2 && cd.nh / cd.nkv <= 2, QTTS_ERR_ARG, "GQA group size must be <= 2");
+    // head shapes, talker and code predictor independently: what the decode attentions have (attention.hip; attn_gq.h for everything beyond
+    // head_dim 128 with a group <= 2) -- the prefill kernels and the GEMMs take any of these
+    auto heads_ok = [](const StackDims& d) {
+        return (d.hd == 64 || d.hd == 128) && d.nh >= 1 && d.nkv >= 1 && d.nh % d.nkv == 0 && d.nh / d.nkv <= 8;
+    };
+    QTTS_REQUIRE(heads_ok(td) && heads_ok(cd), QTTS_ERR_ARG,
+                 "unsupported head shape: talker and code predictor need head_dim 64 or 128 and num_attention_heads = 1..8 x num_key_value_heads "
+                 "(a GQA group of 1..8 query heads per kv head)");
+    // QTTS_ATTN_GQ=1 (read here): EVERY decode-attention launch of this engine runs the general family, so the launches that carry an
+    // attention of their own (cp_attn_o, cp_layer) are off
+    if (attn_gq_env) { cp_attn_o_env = false; cp_layer_env = false; }
     QTTS_REQUIRE(c.max_batch >= 1 && c.max_batch <= 32, QTTS_ERR_LIMIT, "max_batch must be 1..32");
     QTTS_REQUIRE(td.I % 16 == 0 && cd.I % 16 == 0, QTTS_ERR_ARG, "intermediate sizes % 16");
     const int G = c.num_code_groups;
@@ -818,7 +830,7 @@ void qtts_talker::finalize() {
     // 60 s utterance has 0.4 MB of K / V per head and layer (measured 52 us per layer at 800 keys with one workgroup)
     if (const char* e = QTTS_ENV("QTTS_ATTN_NSPLIT")) attn_nsplit = std::max(1, std::min(16, atoi(e)));
     else attn_nsplit = c.max_seq > 512 ? std::min(16, cdiv(c.max_seq, SPLIT_KEYS)) : 1;
-    if (attn_nsplit > 1) attn_part.alloc(attn_part_floats(c.max_batch, td.nkv, attn_nsplit, td.nh / td.nkv) * sizeof(float));
+    if (attn_nsplit > 1) attn_part.alloc(attn_part_floats(c.max_batch, td.nkv, attn_nsplit, td.nh / td.nkv, td.hd) * sizeof(float));
     kv_t.k = kpool_t.p; kv_t.v = vpool_t.p; kv_t.page_table = ptab_t.as<int>();
     kv_c.k = kpool_c.p; kv_c.v = vpool_c.p; kv_c.page_table = ptab_c.as<int>();
 
@@ -993,7 +1005,7 @@ void qtts_talker::frame_step(const qtts_sampling& sp, int eos, int min_new, int 
                              int max_frames, hipStream_t st) {
     const auto& c = cfg;
     const int G = c.num_code_groups;
-    const int64_t fused_before = cp_attn_o_count, mlp_before = cp_mlp_count, layer_before = cp_layer_count, ks_before = ks_split_count;
+    const int64_t fused_before = cp_attn_o_count, mlp_before = cp_mlp_count, layer_before = cp_layer_count, ks_before = ks_split_count, gq_before = attn_gq_count;
     // ---- code predictor: G-1 dependent passes (M:1671-1680, 1250-1312)
     cur_stack = 1;
     for (int j = 0; j < G - 1; ++j) {
@@ -1084,6 +1096,7 @@ void qtts_talker::frame_step(const qtts_sampling& sp, int eos, int min_new, int 
     cp_mlp_per_step = (int)(cp_mlp_count - mlp_before);
     cp_layer_per_step = (int)(cp_layer_count - layer_before);
     ks_split_per_step = (int)(ks_split_count - ks_before);
+    attn_gq_per_step = (int)(attn_gq_count - gq_before);
 }
 
 // A blocking copy of the engine's run-time paths goes through the ENGINE'S stream, never the legacy stream: a `hipMemcpy` orders the legacy stream
@@ -1517,7 +1530,7 @@ int qtts_talker_get_stats(qtts_talker* t, qtts_talker_stats* out) {
     out->cp_fused_giveups = t->cp_fused_giveups; out->cp_fused_capacity = t->fused_capacity; out->cp_fused_active = t->cp_fused_slot ? 1 : 0;
     out->cp_mlp_per_step = t->cp_fused_slot ? t->cp_mlp_per_step : 0;
     out->cp_layer_per_step = t->cp_fused_slot ? t->cp_layer_per_step : 0;
-    out->ks_split_per_step = t->ks_split_env ? t->ks_split_per_step : 0; out->reserved0 = 0;
+    out->ks_split_per_step = t->ks_split_env ? t->ks_split_per_step : 0; out->attn_gq_per_step = t->attn_gq_per_step;
     QTTS_API_END
 }
 int qtts_talker_get_gemm_profile(qtts_talker* t, qtts_gemm_class* out, int32_t cap, int32_t* n) {

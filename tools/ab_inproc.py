@@ -15,6 +15,7 @@ from qwen3_tts_amd.talker import TalkerEngine
 
 CONFIGS = {
     "default": {},
+    "attn_gq": {"QTTS_ATTN_GQ": "1"},            # every decode-attention launch on the general family (csrc/attn_gq.h); the fused attention launches off
     "cp_layer_off": {"QTTS_CP_LAYER": "0"},      # round 6: the layer as its two fused launches (round 5's frame step)
     "layer_gu_entry": {"QTTS_CP_LAYER_GU_WHEN": "0"}, "layer_gu_wo": {"QTTS_CP_LAYER_GU_WHEN": "1"},        # the gate|up block's LDS-DMA at entry / behind the o-projection operator's requests (default: behind the attention stage)
     "layer_hid0": {"QTTS_CP_LAYER_HID_MODE": "0"}, "layer_hid2": {"QTTS_CP_LAYER_HID_MODE": "2"},           # hidden rows: every wave polls its whole quarter / sentinels + a read the L2 may serve (default 1: sentinels + one sc1 read)
