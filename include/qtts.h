@@ -289,7 +289,13 @@ typedef struct {
     float cp_rope_theta;
     /* engine options */
     int32_t weight_dtype; /* QTTS_F32 | QTTS_BF16 (weights and KV cache)            */
-    int32_t max_batch;    /* sequences per generate call                              */
+    /* max_batch: sequences per generate call, 1..64 (QTTS_ERR_LIMIT outside).  A call may bring any smaller batch; the frame step's
+       launches follow the batch of the call.  The KV pools are reserved for max_batch x max_seq at finalize: at max_batch 64, max_seq
+       4096, 1.7B dims (28 layers x 8 kv heads x 128) in bf16 that is 64 x 4096 x 28 x 2 x 8 x 128 x 2 B = 30.1 GB for the talker (plus
+       42 MB for the code predictor) -- max_seq is the lever: 1024 keeps it at 7.5 GB.  Decode scratch above 32 rows grows by the code
+       predictor's two-token first pass only (2 x max_batch rows).  QTTS_SKINNY_WIDE=0 (qtts_set_option; A/B runs) sends that pass's
+       65..128-row GEMMs out as two launches of <= 64 rows instead of one. */
+    int32_t max_batch;
     int32_t max_seq;      /* prompt + generated frames per sequence (KV pages reserved) */
     int32_t use_graph;    /* 1: replay the frame step as a hipGraph; 0: eager launches  */
 } qtts_talker_config;

@@ -96,7 +96,8 @@ struct SkinnyParams {
 };
 void launch_skinny(const SkinnyParams& p, bool bf16, hipStream_t st);
 void skinny_set_launch_events(hipEvent_t start, hipEvent_t stop);   // (bench.py's roofline leg: time the NEXT launch on its own; null = off)
-bool skinny_takes_bf16_x(int M, int K, bool bf16);   // bf16 mode: any M <= 64, K % 32 == 0
+constexpr int SKINNY_MAX_ROWS = 128;                 // 65..128 rows: skinny_wide_kernel / the fp32 kernel's 8-tile form (pass 0 of the code predictor at batch 33..64)
+bool skinny_takes_bf16_x(int M, int K, bool bf16);   // bf16 mode: any M <= 128, K % 32 == 0
 bool skinny_f32_inline_norm(int M, int K);
 bool skinny_f32_splitk_takes(int M, int K_producer, int K_consumer);   // fp32 mode: producer may split K in two, its consumer combines            // fp32 mode: the batch <= 8 kernel takes the RMSNorm row statistics itself (no ss_in)
 bool skinny_ksplit_takes(int M, int N, int K, int fs);   // bf16, batch 17..32: the split-K kernel has an instantiation for this (strip width, shape)

@@ -314,6 +314,187 @@ __global__ __launch_bounds__(NW * 64) void skinny2_kernel(SkinnyParams p) {
     QTTS_TS_END(skinny, 0, p.K, p.N);
 }
 
+// ------------------------------------------------------------------------------------------ bf16, 65..128 rows (pass 0 of the code predictor at batch 33..64)
+// Pass 0 of the code predictor runs two new tokens per request: M = 2 B rows, 66..128 at batch 33..64.  skinny_wide_kernel is skinny2_kernel
+// carried to EIGHT 16-row tiles of x on the same packed operator image: every weight byte crosses HBM once per launch instead of once per
+// 64-row half, and the frame step has one launch where the fallback (two launches of <= 64 rows, QTTS_SKINNY_WIDE=0) has two.
+//   * Arithmetic per row = skinny2_kernel's, bit for bit: the same k-tile-to-wave deal (tile = wave + NW i, consumed in ascending i), one
+//     v_mfma_f32_16x16x32_bf16 chain per (strip, m-tile), X.X^T on the matrix pipe for the RMSNorm statistic (NORM), partial sums added in
+//     ascending wave order, the same epilogue expressions.  A row's result does not depend on how many rows travel with it.
+//   * Registers (8 waves: 256 per lane): 8 m-tiles x SPW accumulators (+ 8 for X.X^T) leave room for two chunks of U k-tiles in flight --
+//     U = 1 when the statistic or a strip pair is carried (96 accumulator + 80 operand registers), U = 2 for the plain o- / down-projections
+//     in narrow strips (32 + 144; with 16-feature strips that instantiation spilled: it keeps U = 1).  Only the m-tiles that hold rows (wave-uniform `m < mtiles`) are requested and multiplied: 5 of 8 at M = 66.
+//   * The cross-wave combine goes through LDS in two halves of four m-tiles ([NW][4 (SPW + NORM)][64] x 16 B: 96 KB at most -- all eight
+//     at once would need 192 KB), and wave w < 4 owns m-tile 4 h + w of half h: four waves run the epilogue side by side and each fetches
+//     the residual / bias of its own two m-tiles at entry, under the weight stream.
+//   * x is the producer's bf16 copy (the frame step always has one); rows >= M of a ragged tile re-read row 0 (their sums are never stored).
+template <int SPW, int NW, int FS, int U, bool EXACT, bool NORM>
+__global__ __launch_bounds__(NW * 64) void skinny_wide_kernel(SkinnyParams p) {
+    constexpr int MT = 8, MH = 4, KT = 32;
+    constexpr int NSH = (SPW + (NORM ? 1 : 0)) * MH;             // LDS slots per wave and half: the GEMM's + one X.X^T per m-tile
+    static_assert(NW >= MH, "skinny_wide: one epilogue wave per m-tile of a half");
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_sk[];
+    f32x4* red = reinterpret_cast<f32x4*>(smem_sk);              // [NW][NSH][64]
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int lj = lane & 15, lq = lane >> 4;
+    const int nkt = p.K / KT;
+    const int my_tiles = (nkt - wave + NW - 1) / NW;             // tile = wave + NW*i
+    const int nchunks = (my_tiles + U - 1) / U;
+    const int strip0 = blockIdx.x * SPW;
+    const int mtiles = __builtin_amdgcn_readfirstlane((p.M + 15) >> 4);      // 5..8
+
+    f32x4 acc[SPW][MT], acc_ss[NORM ? MT : 1];
+#pragma unroll
+    for (int m = 0; m < MT; ++m) {
+        if constexpr (NORM) acc_ss[m] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int s = 0; s < SPW; ++s) acc[s][m] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    }
+
+    const bool wlane = lj < FS;                                  // lanes that own a weight row issue the weight requests (skinny2_kernel)
+    const u32x4* wbase[SPW];
+#pragma unroll
+    for (int s = 0; s < SPW; ++s)
+        wbase[s] = reinterpret_cast<const u32x4*>(p.Wp) + ((size_t)(strip0 + s) * nkt) * (FS * 4) + lq * FS + (wlane ? lj : 0);
+    // B operand of tile kt, m-tile m: lane (lj, lq) <- x[m*16 + lj][kt*32 + lq*8 .. +8]
+    // (32-bit element offsets from one base: M x ldx < 2^31 is checked at launch -- eight 64-bit pointers would cost 8 more registers)
+    const unsigned short* xbase = reinterpret_cast<const unsigned short*>(p.x) + lq * 8;
+    unsigned xoff[MT];
+#pragma unroll
+    for (int m = 0; m < MT; ++m) xoff[m] = (unsigned)(m * 16 + lj < p.M ? m * 16 + lj : 0) * (unsigned)p.ldx;
+
+    auto load_chunk = [&](u32x4 (&w)[SPW][U], u32x4 (&xq)[MT][U], int c) {
+        const int n = EXACT ? U : my_tiles - c * U;              // wave-uniform: tiles of this chunk that exist
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            if (EXACT || u < n) {
+                const int kt = wave + NW * (c * U + u);
+                if (FS == 16 || wlane) {
+#pragma unroll
+                    for (int s = 0; s < SPW; ++s) w[s][u] = skinny_wload(wbase[s] + (size_t)kt * (FS * 4));
+                }
+#pragma unroll
+                for (int m = 0; m < MT; ++m)
+                    if (m < mtiles) xq[m][u] = *reinterpret_cast<const u32x4*>(xbase + xoff[m] + kt * KT);
+            }
+        }
+    };
+
+    // ---- 1. the weight stream and this wave's x fragments start first: two chunks in flight, ping-pong
+    u32x4 wR[2][SPW][U], xR[2][MT][U];
+#pragma unroll
+    for (int k = 0; k < 2; ++k)
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+#pragma unroll
+            for (int s = 0; s < SPW; ++s) wR[k][s][u] = (u32x4){0u, 0u, 0u, 0u};
+#pragma unroll
+            for (int m = 0; m < MT; ++m) xR[k][m][u] = (u32x4){0u, 0u, 0u, 0u};
+        }
+    load_chunk(wR[0], xR[0], 0);
+    if (!EXACT || nchunks > 1) load_chunk(wR[1], xR[1], 1);
+
+    // ---- 2. epilogue operands of waves 0..3 (m-tiles w and 4 + w) are fetched now, under the weight stream
+    f32x4 resv[SPW][2], biasv[SPW];
+    const bool epi_wave = wave < MH;
+#pragma unroll
+    for (int s = 0; s < SPW; ++s) {
+        const int col = (p.act == ACT_SWIGLU ? blockIdx.x * 16 : (strip0 + s) * FS) + lq * 4;
+        biasv[s] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        if (epi_wave && p.bias && lq * 4 < FS) biasv[s] = *reinterpret_cast<const f32x4*>(p.bias + (strip0 + s) * FS + lq * 4);
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            resv[s][h] = (f32x4){0.f, 0.f, 0.f, 0.f};
+            const int row = (h * MH + wave) * 16 + lj;
+            if (epi_wave && p.res && row < p.M && lq * 4 < FS && (p.act != ACT_SWIGLU || s == 0))
+                resv[s][h] = *reinterpret_cast<const f32x4*>(p.res + (size_t)row * p.ldr + col);
+        }
+    }
+    const int done = p.done_flag ? *p.done_flag : 0;
+    if (done) return;
+
+    auto compute_tile = [&](u32x4 (&w)[SPW][U], u32x4 (&xq)[MT][U], int u) {
+#pragma unroll
+        for (int m = 0; m < MT; ++m) {
+            if (m < mtiles) {
+                bf16x8 xb;
+                *reinterpret_cast<u32x4*>(&xb) = xq[m][u];
+#pragma unroll
+                for (int s = 0; s < SPW; ++s) {
+                    bf16x8 wa;
+                    *reinterpret_cast<u32x4*>(&wa) = w[s][u];
+                    acc[s][m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa, xb, acc[s][m], 0, 0, 0);
+                }
+                if constexpr (NORM) acc_ss[m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xb, xb, acc_ss[m], 0, 0, 0);
+            }
+        }
+    };
+    auto compute_chunk = [&](u32x4 (&w)[SPW][U], u32x4 (&xq)[MT][U], int c) {
+        const int n = EXACT ? U : my_tiles - c * U;
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+            if (EXACT || u < n) compute_tile(w, xq, u);
+    };
+
+    // ---- 3. consume: the chunk after next is requested as soon as a buffer frees up
+    for (int c = 0; c < nchunks; c += 2) {
+        compute_chunk(wR[0], xR[0], c);
+        if (c + 2 < nchunks) load_chunk(wR[0], xR[0], c + 2);
+        if (c + 1 < nchunks) compute_chunk(wR[1], xR[1], c + 1);
+        if (c + 3 < nchunks) load_chunk(wR[1], xR[1], c + 3);
+    }
+
+    // ---- 4. cross-wave combine (fixed order) and epilogue, one half of the m-tiles at a time
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        if (h) __syncthreads();                                  // half 0 has been read
+#pragma unroll
+        for (int i = 0; i < MH; ++i) {
+#pragma unroll
+            for (int s = 0; s < SPW; ++s) red[(wave * NSH + s * MH + i) * 64 + lane] = acc[s][h * MH + i];
+            if constexpr (NORM) red[(wave * NSH + SPW * MH + i) * 64 + lane] = acc_ss[h * MH + i];
+        }
+        __syncthreads();
+        const int row = (h * MH + wave) * 16 + lj;               // wave w < 4: m-tile 4 h + w
+        if (wave < MH && h * MH + wave < mtiles) {
+            float rstd = 1.f;
+            if constexpr (NORM) {
+                // X.X^T: the diagonal element of row lj sits in lane (lj, lj >> 2), component lj & 3
+                const float* rf = reinterpret_cast<const float*>(red);
+                const int src = (((lj >> 2) * 16 + lj) << 2) + (lj & 3);
+                float ssum = rf[((0 * NSH + SPW * MH + wave) * 64) * 4 + src];
+#pragma unroll
+                for (int w2 = 1; w2 < NW; ++w2) ssum += rf[((w2 * NSH + SPW * MH + wave) * 64) * 4 + src];     // fixed order
+                rstd = rsqrtf(ssum / (float)p.K + p.eps);
+            }
+            f32x4 v[SPW];
+#pragma unroll
+            for (int s = 0; s < SPW; ++s) {
+                f32x4 t = red[(0 * NSH + s * MH + wave) * 64 + lane];
+#pragma unroll
+                for (int w2 = 1; w2 < NW; ++w2) t += red[(w2 * NSH + s * MH + wave) * 64 + lane];
+                v[s] = t * rstd + biasv[s];
+            }
+            if (row < p.M && lq * 4 < FS) {
+                if (p.act == ACT_SWIGLU) {
+                    if constexpr (SPW == 2) {
+                        f32x4 o;
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) o[r] = (v[0][r] / (1.f + expf(-v[0][r]))) * v[1][r];
+                        o += resv[0][h];
+                        skinny_store4(p, row, blockIdx.x * 16 + lq * 4, o, false);
+                    }
+                } else {
+#pragma unroll
+                    for (int s = 0; s < SPW; ++s) skinny_store4(p, row, (strip0 + s) * FS + lq * 4, v[s] + resv[s][h], true);
+                }
+            }
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------ bf16, batch 17..32, deep K: split-K (round 6)
 // At batch 17..32 (two 16-row tiles of x) a workgroup of skinny2_kernel pulls M x K x 2 B of x whatever its strip width: the talker's
 // down-projection (K = 6144, 256 workgroups of ONE 8-feature strip) moves 393 KB of x against 98 KB of weights per workgroup -- 100 MB
@@ -996,9 +1177,9 @@ __global__ __launch_bounds__(NW * 64) void skinny8_f32_kernel(const void* kWp, c
     }
 }
 
-// bf16 mode: a GEMM input may arrive as the producer's bf16 copy (x_bf16) for any M <= 64 -- nothing is staged through LDS any
+// bf16 mode: a GEMM input may arrive as the producer's bf16 copy (x_bf16) for any M <= 128 -- nothing is staged through LDS any
 // more, so there is no capacity condition left (round 1: M <= 16 up to K = 7096, M <= 32 up to K = 2344).
-bool skinny_takes_bf16_x(int M, int K, bool bf16) { return bf16 && M >= 1 && M <= 64 && K % 32 == 0; }
+bool skinny_takes_bf16_x(int M, int K, bool bf16) { return bf16 && M >= 1 && M <= SKINNY_MAX_ROWS && K % 32 == 0; }
 // ACT_SWIGLU8 lives in skinny8_kernel only: the K for which that kernel is instantiated (launch8_nw)
 bool skinny_swiglu8_takes(int K) { return K == 1024 || K == 2048 || K == 3072 || K == 6144; }
 
@@ -1063,12 +1244,62 @@ template <int MT, int SPW, int NW>
 static void launch_f32_one(const SkinnyParams& p, hipStream_t st) {
     const int grid = p.N / (16 * SPW);
     const size_t lds = (size_t)NW * SPW * MT * 64 * 16;
-    QTTS_SK_LAUNCH((skinny_f32_kernel<MT, SPW, NW>), dim3(grid), dim3(NW * 64), lds, st, p);
+    auto kern = skinny_f32_kernel<MT, SPW, NW>;
+    if (lds > 64 * 1024) ensure_dynamic_lds(reinterpret_cast<const void*>(kern), 160 * 1024);      // (8 m-tiles: 64 KB, strip pairs 128 KB; <= 4 m-tiles stay within 64 KB, as before)
+    QTTS_SK_LAUNCH(kern, dim3(grid), dim3(NW * 64), lds, st, p);
 }
 template <int MT>
 static void launch_f32_mt(const SkinnyParams& p, int spw, int nw, hipStream_t st) {
     if (nw == 8) { if (spw == 2) launch_f32_one<MT, 2, 8>(p, st); else launch_f32_one<MT, 1, 8>(p, st); }
     else         { if (spw == 2) launch_f32_one<MT, 2, 4>(p, st); else launch_f32_one<MT, 1, 4>(p, st); }
+}
+
+// 65..128 rows, bf16 x: skinny_wide_kernel.  Chunk depth by what the accumulators leave (see the kernel); EXACT as for skinny2_kernel: 8 waves and
+// every wave owns the same number of k-tiles, a multiple of U (all shapes of the real models).
+template <int SPW, int NW, int FS, int U, bool EXACT, bool NORM>
+static void launch_wide_n(const SkinnyParams& p, hipStream_t st) {
+    const int grid = p.N / (FS * SPW);
+    const size_t lds = (size_t)NW * (SPW + (NORM ? 1 : 0)) * 4 * 64 * 16;
+    QTTS_REQUIRE((size_t)p.M * p.ldx < ((size_t)1 << 31), QTTS_ERR_LIMIT, "skinny: x rows of the 65..128-row kernel must lie within 2^31 elements");
+    auto kern = skinny_wide_kernel<SPW, NW, FS, U, EXACT, NORM>;
+    if (lds > 48 * 1024) ensure_dynamic_lds(reinterpret_cast<const void*>(kern), 160 * 1024);
+    QTTS_SK_LAUNCH(kern, dim3(grid), dim3(NW * 64), lds, st, p);
+}
+template <int SPW, int NW, int FS, bool NORM>
+static void launch_wide_x(const SkinnyParams& p, hipStream_t st) {
+    constexpr int U = (SPW == 1 && !NORM && FS < 16) ? 2 : 1;
+    if constexpr (NW == 8) {
+        const int nkt = p.K / 32;
+        if (nkt % NW == 0 && (nkt / NW) % U == 0) { launch_wide_n<SPW, NW, FS, U, true, NORM>(p, st); return; }
+    }
+    launch_wide_n<SPW, NW, FS, U, false, NORM>(p, st);
+}
+template <int SPW, int FS>
+static void launch_wide_fs(const SkinnyParams& p, int nw, hipStream_t st) {
+    if (nw == 8) { if (p.norm) launch_wide_x<SPW, 8, FS, true>(p, st); else launch_wide_x<SPW, 8, FS, false>(p, st); }
+    else         { if (p.norm) launch_wide_x<SPW, 4, FS, true>(p, st); else launch_wide_x<SPW, 4, FS, false>(p, st); }
+}
+static void launch_skinny_wide(const SkinnyParams& p, int spw, int fs, int nw, hipStream_t st) {
+    if (spw == 2) launch_wide_fs<2, 16>(p, nw, st);
+    else if (fs == 16) launch_wide_fs<1, 16>(p, nw, st);
+    else if (fs == 8) launch_wide_fs<1, 8>(p, nw, st);
+    else launch_wide_fs<1, 4>(p, nw, st);
+}
+// QTTS_SKINNY_WIDE=0 (A/B runs, the equality tests) and bf16 launches without a bf16 copy of x: rows 0..R-1 and R..M-1 as two launches of the
+// <= 64-row kernels.  Rows are independent (in-place residual updates included) and skinny2_kernel / skinny_f32_kernel sum a row in the
+// same order whatever their m-tile count: same bits.  R = 64, or 48 where that would leave <= 8 rows: the batch <= 8 kernels deal k-tile
+// PAIRS to the waves -- another order.
+static void launch_skinny_halves(const SkinnyParams& p, bool bf16, hipStream_t st) {
+    SkinnyParams a = p, b = p;
+    const int R = p.M - 64 > 8 ? 64 : 48;
+    a.M = R; b.M = p.M - R;
+    b.x = p.x_bf16 ? reinterpret_cast<const float*>(reinterpret_cast<const unsigned short*>(p.x) + (size_t)R * p.ldx) : p.x + (size_t)R * p.ldx;
+    b.out = p.out_bf16 ? reinterpret_cast<float*>(reinterpret_cast<unsigned short*>(p.out) + (size_t)R * p.ldo) : p.out + (size_t)R * p.ldo;
+    if (p.out16) b.out16 = reinterpret_cast<unsigned short*>(p.out16) + (size_t)R * p.ldo;
+    if (p.res) b.res = p.res + (size_t)R * p.ldr;
+    if (p.ss_in) b.ss_in = p.ss_in + R;
+    launch_skinny(a, bf16, st);
+    launch_skinny(b, bf16, st);
 }
 
 // batch 17..32, no norm, plain epilogue: the split-K kernel (round 6).  Instantiations = the o- and down-projections of the released
@@ -1269,7 +1500,7 @@ void launch_skinny(const SkinnyParams& p, bool bf16, hipStream_t st) {
     QTTS_REQUIRE(fs == 16 || bf16, QTTS_ERR_ARG, "skinny: narrow strips (fs < 16) are only built for the bf16 kernel");
     QTTS_REQUIRE(p.N % 16 == 0, QTTS_ERR_ARG, "skinny: N % 16");
     QTTS_REQUIRE(p.K % KT == 0, QTTS_ERR_ARG, "skinny: K must be a multiple of the k-tile");
-    QTTS_REQUIRE(p.M >= 1 && p.M <= 64, QTTS_ERR_LIMIT, "skinny: 1 <= M <= 64");
+    QTTS_REQUIRE(p.M >= 1 && p.M <= SKINNY_MAX_ROWS, QTTS_ERR_LIMIT, "skinny: 1 <= M <= 128");
 #if !QTTS_ABLATE
     QTTS_REQUIRE(p.ablate == 0, QTTS_ERR_ARG, "skinny: perf-ablation flags need the `ablate` build variant (python qwen3-tts_amd/build.py --variant ablate)");
 #endif
@@ -1289,6 +1520,14 @@ void launch_skinny(const SkinnyParams& p, bool bf16, hipStream_t st) {
     }
     const int spw = skinny_spw(p.N, fs, p.act == ACT_SWIGLU);
     const int nw = (p.K / KT >= 16) ? 8 : 4;     // 8 waves split K unless K is tiny
+    if (p.M > 64) {                      // pass 0 of the code predictor at batch 33..64: 8 m-tiles in one launch, or (QTTS_SKINNY_WIDE=0) two halves
+        QTTS_REQUIRE(p.ksplit == 0 && !p.xp && !QTTS_ABL(p, 15), QTTS_ERR_ARG, "skinny: split-K / combine / ablation are batch <= 64 forms");
+        if (!QTTS_OPT_ON("QTTS_SKINNY_WIDE") || (bf16 && !p.x_bf16)) { launch_skinny_halves(p, bf16, st); return; }
+        if (bf16) launch_skinny_wide(p, spw, fs, nw, st);
+        else launch_f32_mt<8>(p, spw, nw, st);
+        QTTS_CHECK_HIP(hipGetLastError());
+        return;
+    }
     const int mt = p.M <= 16 ? 1 : (p.M <= 32 ? 2 : 4);
     if (bf16 && nw == 8 && mt == 1 && launch_skinny8(p, spw, fs, st)) { QTTS_CHECK_HIP(hipGetLastError()); return; }
     if (bf16 && mt == 2 && launch_skinny_ks(p, fs, st)) { QTTS_CHECK_HIP(hipGetLastError()); return; }

@@ -262,8 +262,9 @@ struct qtts_talker {
         upload_packed(L.o_p, ow, d.H, d.qd, nullptr, L.fs_o);
         upload_packed(L.gu_p, guw, 2 * d.I, d.H, &PS(p + "post_attention_layernorm.weight", {d.H}));
         // (only engines that can run at batch <= 8 at all pay for the second copy -- 1.46 GB at 1.7B dims; an engine created for waves
-        // of 9..32 rows keeps the strip-pair kernel for a short last wave: ADVICE r3)
-        if (bf16 && swiglu8_env && cfg.max_batch <= 8 && d.I % 8 == 0 && skinny_swiglu8_takes(d.H))
+        // of 9..32 rows keeps the strip-pair kernel for a short last wave: ADVICE r3; an engine created for 33..64 rows follows the live batch
+        // of every call and runs a call of <= 8 rows exactly as an engine created for 8 does)
+        if (bf16 && swiglu8_env && (cfg.max_batch <= 8 || cfg.max_batch > 32) && d.I % 8 == 0 && skinny_swiglu8_takes(d.H))
             upload_packed(L.gu_p8, interleave_gu8(PS(p + "mlp.gate_proj.weight", {d.I, d.H}), PS(p + "mlp.up_proj.weight", {d.I, d.H}), d.I, d.H),
                           2 * d.I, d.H, &PS(p + "post_attention_layernorm.weight", {d.H}));
         upload_packed(L.d_p, dw, d.H, d.I, nullptr, L.fs_d);
@@ -685,11 +686,13 @@ void qtts_talker::finalize() {
     // QTTS_ATTN_GQ=1 (read here): EVERY decode-attention launch of this engine runs the general family, so the launches that carry an
     // attention of their own (cp_attn_o, cp_layer) are off
     if (attn_gq_env) { cp_attn_o_env = false; cp_layer_env = false; }
-    QTTS_REQUIRE(c.max_batch >= 1 && c.max_batch <= 32, QTTS_ERR_LIMIT, "max_batch must be 1..32");
+    QTTS_REQUIRE(c.max_batch >= 1 && c.max_batch <= 64, QTTS_ERR_LIMIT, "max_batch must be 1..64");
     QTTS_REQUIRE(td.I % 16 == 0 && cd.I % 16 == 0, QTTS_ERR_ARG, "intermediate sizes % 16");
     const int G = c.num_code_groups;
     if (c.cp_num_hidden_layers > CP_FUSED_MAX_LAYERS) { cp_mlp_env = false; cp_attn_o_env = false; }     // (tag uniqueness, see CP_FUSED_MAX_LAYERS)
-    if (!cp_mlp_instantiated(cd.H, cd.I, bf16) || c.max_batch > 8) cp_mlp_env = false;
+    // (engines created for 9..32 rows keep the separate launches at batch <= 8, as before; engines created for 33..64 rows decide by the live
+    // batch of the call: cp_mlp_takes / cp_mlp32_takes in decode_layer, and hold the share of the larger launch)
+    if (!cp_mlp_instantiated(cd.H, cd.I, bf16) || (c.max_batch > 8 && c.max_batch <= 32)) cp_mlp_env = false;
     // the 32-row form: bf16 engines created for more than 8 rows, at most CP_FUSED_MAX_LAYERS layers (tag uniqueness)
     if (!bf16 || c.max_batch <= 8 || c.cp_num_hidden_layers > CP_FUSED_MAX_LAYERS || !cp_mlp32_instantiated(cd.H, cd.I)) cp_mlp32_env = false;
     // fp32 engines (the exact parity mode) take the fused MLP launch only on request (QTTS_CP_MLP_F32=1): cp_mlp_kernel<true, ...> is the fused
@@ -710,7 +713,8 @@ void qtts_talker::finalize() {
         if (cp_mlp_env) { grid_cp = std::max(grid_cp, cp_mlp_grid(cd.H)); occ_ok = occ_ok && cp_mlp_blocks_per_cu(cd.H, cd.I, bf16) >= 1; }
         if (cp_mlp32_env) { grid_cp = std::max(grid_cp, cp_mlp_grid(cd.H)); occ_ok = occ_ok && cp_mlp32_blocks_per_cu(cd.H, cd.I) >= 1; }
         if (want_layer && cp_layer_blocks_per_cu(cd.H, cd.I, bf16) < 1) want_layer = false;      // (also sets the kernels' dynamic-LDS attribute, outside any capture)
-        if (want_layer) fused_admit(grid_cp, occ_ok, bf16 ? CP_SHARE_LAYER : CP_SHARE_LAYER_F32, cp_layer_lds_bytes(cd.H, cd.I, bf16),
+        if (want_layer) fused_admit(grid_cp, occ_ok, std::max(bf16 ? CP_SHARE_LAYER : CP_SHARE_LAYER_F32, cp_mlp32_env ? CP_SHARE_MLP32 : 0),
+                                    std::max(cp_layer_lds_bytes(cd.H, cd.I, bf16), cp_mlp32_env ? CP_LDS_MLP32 : 0),
                                     CU_REG_BUDGET - CU_REG_BUDGET / 8, CU_LDS_BUDGET / 2);
         if (!cp_fused_slot) {         // no room for (or no) layer launch: the two launches' smaller shares
             want_layer = false;
@@ -834,14 +838,15 @@ void qtts_talker::finalize() {
     kv_t.k = kpool_t.p; kv_t.v = vpool_t.p; kv_t.page_table = ptab_t.as<int>();
     kv_c.k = kpool_c.p; kv_c.v = vpool_c.p; kv_c.page_table = ptab_c.as<int>();
 
-    // ---- decode scratch (rows <= 64)
-    const int R = 64;
-    x16.alloc((size_t)R * td.H * 2); cp_x16.alloc((size_t)R * cd.H * 2); ph16.alloc((size_t)R * td.H * 2); cp_in16.alloc((size_t)R * td.H * 2);
+    // ---- decode scratch (rows <= 64; what pass 0 of the code predictor touches -- two new tokens per request -- holds 2 max_batch rows:
+    // R2 = 64 for engines of up to 32 rows, as before)
+    const int R = 64, R2 = std::max(R, 2 * c.max_batch);
+    x16.alloc((size_t)R * td.H * 2); cp_x16.alloc((size_t)R2 * cd.H * 2); ph16.alloc((size_t)R * td.H * 2); cp_in16.alloc((size_t)R2 * td.H * 2);
     x.alloc((size_t)R * td.H * 4); qkv.alloc((size_t)R * (td.qd + 2 * td.kvd) * 4); att.alloc((size_t)R * td.qd * 4);
     act.alloc((size_t)R * td.I * 4); logits.alloc((size_t)R * c.vocab_size * 4); past_hidden.alloc((size_t)R * td.H * 4);
-    cp_in.alloc((size_t)R * td.H * 4); cp_x.alloc((size_t)R * cd.H * 4); cp_qkv.alloc((size_t)R * (cd.qd + 2 * cd.kvd) * 4);
-    cp_att.alloc((size_t)R * cd.qd * 4); cp_act.alloc((size_t)R * cd.I * 4); cp_logits.alloc((size_t)(c.num_code_groups - 1) * R * c.cp_vocab_size * 4);     // [pass][row][cp vocab]: every pass keeps its own rows (qtts_talker_debug_cp_logits)
-    cur_tok.alloc(R * 4); sub.alloc((size_t)R * G * 4); ss_rows.alloc(64 * 8); ints.alloc(64 * 4 + R * 4);
+    cp_in.alloc((size_t)R2 * td.H * 4); cp_x.alloc((size_t)R2 * cd.H * 4); cp_qkv.alloc((size_t)R2 * (cd.qd + 2 * cd.kvd) * 4);
+    cp_att.alloc((size_t)R2 * cd.qd * 4); cp_act.alloc((size_t)R2 * cd.I * 4); cp_logits.alloc((size_t)(c.num_code_groups - 1) * R * c.cp_vocab_size * 4);     // [pass][row][cp vocab]: every pass keeps its own rows (qtts_talker_debug_cp_logits)
+    cur_tok.alloc(R * 4); sub.alloc((size_t)R * G * 4); ss_rows.alloc((size_t)R2 * 8); ints.alloc(64 * 4 + R * 4);
     if (!bf16) {                      // the two halves of a split-K o- / down-projection (decode_layer)
         const size_t hmax = (size_t)std::max(td.H, cd.H);
         sk_part.alloc(2 * 8 * hmax * 4);

@@ -270,6 +270,7 @@ class TalkerEngine:
         B, T, H = inputs_embeds.shape
         if B > self.max_batch:
             raise ValueError(f"batch {B} exceeds max_batch {self.max_batch} given at construction")
+        self._live_batch = int(B)
         if teacher_codes is not None:
             if teacher_codes.dim() != 3 or teacher_codes.shape[0] != B or teacher_codes.shape[2] != c.num_code_groups:
                 raise ValueError(f"teacher_codes must be (B, F, {c.num_code_groups})")
@@ -373,6 +374,7 @@ class TalkerEngine:
         B, T, H = inputs_embeds.shape
         if B > self.max_batch:
             raise ValueError(f"batch {B} exceeds max_batch {self.max_batch} given at construction")
+        self._live_batch = int(B)
         if packet_frames < 1:
             raise ValueError("packet_frames must be >= 1")
         mask = attention_mask.to("cpu", torch.long)
@@ -441,8 +443,10 @@ class TalkerEngine:
 
     @_lib.locked
     def debug_cp_logits(self) -> torch.Tensor:
-        """(num_code_groups - 1, max_batch, cp_vocab): the code predictor's raw logits of the last frame step that ran, every pass."""
-        out = torch.empty(self.config.num_code_groups - 1, self.max_batch, self.config.cp_vocab_size, dtype=torch.float32, device=self.device)
+        """(num_code_groups - 1, B, cp_vocab): the code predictor's raw logits of the last frame step that ran, every pass; B is the batch
+        of the last call (the engine packs pass j at j * B * cp_vocab with that live B, not with max_batch)."""
+        B = getattr(self, "_live_batch", self.max_batch)
+        out = torch.empty(self.config.num_code_groups - 1, B, self.config.cp_vocab_size, dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
             _lib.check(self._lib.qtts_talker_debug_cp_logits(self._h, C.c_void_p(out.data_ptr()), self._s()))
             self._stream.synchronize()
