@@ -48,8 +48,9 @@ const char* qtts_last_error(void);
  * 9: + qtts_codec_get_stats; 10: + qtts_set_option / qtts_get_option, qtts_talker_stats grew the fused-launch fields;
  * 11: + qtts_talker_debug_cp_logits, qtts_talker_stats.cp_layer_per_step in the reserved word;
  * 12: + qtts_talker_stats.ks_split_per_step (appended); 13: qtts_talker_stats.attn_gq_per_step in the reserved word, the talker
- * engine takes head_dim 64 | 128 and GQA groups of 1..8). */
-#define QTTS_ABI_VERSION 13
+ * engine takes head_dim 64 | 128 and GQA groups of 1..8; 14: + qtts_row_sampling, qtts_talker_generate_rows,
+ * qtts_talker_stream_begin_rows, qtts_talker_stats.graph_captures / row_table_last (appended)). */
+#define QTTS_ABI_VERSION 14
 int qtts_abi_version(void);
 
 /* A/B switches of the library (measuring tools and tests; a deployment sets none).  Every switch has a name of the form
@@ -314,6 +315,32 @@ typedef struct {
     uint64_t seed;   /* Philox key; torch's global-RNG stream cannot be reproduced across devices */
 } qtts_sampling;
 
+/* The same knobs for ONE request of a batch, plus the request's own length limits (qtts_talker_generate_rows, ABI v14).  The reference
+ * resolves these per call (user value > generate_config.json > hard default, qwen_tts/inference/qwen3_tts_model.py:287-352) and hands
+ * one set to the whole batch; a service that batches requests of different callers needs them per request.
+ *   seed            Philox key of THIS request: its draws are a function of (seed, step, codebook) and not of the row it occupies or
+ *                   of the requests it is batched with.  Two rows with the SAME seed therefore draw the same numbers: give every
+ *                   request its own (the Python layer does when the caller passes one seed or none).
+ *   max_new_tokens  the request's own limit (>= 1).  A row that reaches it is treated like a row that hit EOS: it yields
+ *                   max_new_tokens - 1 frames -- what a scalar call with that limit yields -- and receives eos from token index
+ *                   max_new_tokens - 1 on (the one visible difference from a scalar run, whose last token is the sampled one).
+ *   min_new_tokens  EOS is blocked for this request until it has that many tokens. */
+typedef struct qtts_row_sampling {
+    int32_t do_sample;
+    int32_t top_k;   /* 0 = off */
+    float top_p;     /* 1.0 = off; (0, 1] on a sampling row */
+    float temperature;
+    float repetition_penalty;
+    int32_t subtalker_dosample;
+    int32_t subtalker_top_k;
+    float subtalker_top_p;
+    float subtalker_temperature;
+    int32_t max_new_tokens;
+    int32_t min_new_tokens;
+    int32_t reserved;
+    uint64_t seed;
+} qtts_row_sampling;
+
 int qtts_talker_create(const qtts_talker_config* cfg, qtts_talker** out);
 void qtts_talker_destroy(qtts_talker* t);
 /* `name` = reference state_dict key relative to `talker.` (e.g. "model.layers.0.self_attn.q_proj.weight",
@@ -371,6 +398,19 @@ int qtts_talker_generate(qtts_talker* t, const qtts_sampling* sp, int32_t max_ne
                          int64_t* codes_dev, float* hidden_dev, int64_t* tokens_dev, int32_t* n_frames_host,
                          void* stream);
 
+/* qtts_talker_generate with per-request settings (ABI v14; knobs as qwen_tts/inference/qwen3_tts_model.py:287-352 resolves them, here
+ * one set per row): rows_host[b] holds row b's knobs, seed and limits; n_rows must equal the prefilled batch.  The settings live in a
+ * device table the samplers read, so they are NOT part of the captured frame graph: calls that differ only in the table's values
+ * replay the same graph (qtts_talker_stats.graph_captures does not advance).  Buffers are sized by the LARGEST max_new_tokens of the
+ * table (codes_dev (B, max-1, G), hidden_dev (B, max-1, H), tokens_dev (B, max)); *n_frames_host is the call's frame count: the
+ * generation stops when every row hit EOS or its own limit.  Row b's frames end before its first eos in codebook 0 (as
+ * modeling_qwen3_tts.py:2283-2289 trims them).  Refused: n_rows != B, top_p outside (0, 1] on a sampling row, temperature <= 0,
+ * max_new_tokens < 1 (QTTS_ERR_ARG, the message names the row); prompt + the largest limit beyond max_seq (QTTS_ERR_LIMIT); teacher
+ * forcing or profile mode 2 together with a table (QTTS_ERR_ARG). */
+int qtts_talker_generate_rows(qtts_talker* t, const qtts_row_sampling* rows_host, int32_t n_rows, int32_t eos_token_id,
+                              const int32_t* suppress_host, int32_t n_suppress, int64_t* codes_dev, float* hidden_dev,
+                              int64_t* tokens_dev, int32_t* n_frames_host, void* stream);
+
 /* Resumable generation -- qtts_talker_generate in three calls, for streaming OUTPUT (BASELINE config 4; the reference
  * only "simulates streaming text input", qwen3_tts_model.py:513-515, and returns whole utterances):
  *   stream_begin  after qtts_talker_prefill: same arguments as qtts_talker_generate minus the outputs that only exist at
@@ -385,6 +425,9 @@ int qtts_talker_generate(qtts_talker* t, const qtts_sampling* sp, int32_t max_ne
 int qtts_talker_stream_begin(qtts_talker* t, const qtts_sampling* sp, int32_t max_new_tokens, int32_t min_new_tokens,
                              int32_t eos_token_id, const int32_t* suppress_host, int32_t n_suppress, int64_t* codes_dev,
                              float* hidden_dev, void* stream);
+/* stream_begin with per-request settings (see qtts_talker_generate_rows); stream_step / stream_end are the same calls. */
+int qtts_talker_stream_begin_rows(qtts_talker* t, const qtts_row_sampling* rows_host, int32_t n_rows, int32_t eos_token_id,
+                                  const int32_t* suppress_host, int32_t n_suppress, int64_t* codes_dev, float* hidden_dev, void* stream);
 int qtts_talker_stream_step(qtts_talker* t, int32_t max_frames_now, int32_t* frames_total_host, int32_t* finished_host,
                             void* stream);
 int qtts_talker_stream_end(qtts_talker* t, int64_t* tokens_dev, int32_t* n_frames_host, void* stream);
@@ -419,6 +462,8 @@ typedef struct {
                                      * bf16 engines at batch 17..32: the o- / down-projections; ABI v12)                                       */
     int32_t attn_gq_per_step;       /* decode-attention launches of that frame step that ran the general kernel family (attn_gq.h: any head shape beyond
                                      * head_dim 128 with a group <= 2, or every launch under QTTS_ATTN_GQ=1; ABI v13: the former reserved word) */
+    int32_t row_table_last;         /* 1: the last generation ran with a per-row settings table (qtts_talker_generate_rows; ABI v14) */
+    int64_t graph_captures;         /* frame-graph captures over the engine's life: a call that replays a cached graph adds none (ABI v14) */
 } qtts_talker_stats;
 int qtts_talker_get_stats(qtts_talker* t, qtts_talker_stats* out);
 /* Per-class result of the profile mode (qtts_talker_set_profile(t, 1), ABI v8): every launch of the decode GEMM in frames 1..6

@@ -46,6 +46,15 @@ class SamplingC(C.Structure):
                 ("subtalker_temperature", C.c_float), ("seed", C.c_uint64)]
 
 
+class RowSamplingC(C.Structure):
+    """include/qtts.h qtts_row_sampling: one request's knobs, limits and seed (qtts_talker_generate_rows)."""
+    _fields_ = [("do_sample", C.c_int32), ("top_k", C.c_int32), ("top_p", C.c_float), ("temperature", C.c_float),
+                ("repetition_penalty", C.c_float), ("subtalker_dosample", C.c_int32),
+                ("subtalker_top_k", C.c_int32), ("subtalker_top_p", C.c_float),
+                ("subtalker_temperature", C.c_float), ("max_new_tokens", C.c_int32), ("min_new_tokens", C.c_int32),
+                ("reserved", C.c_int32), ("seed", C.c_uint64)]
+
+
 class EncoderConfigC(C.Structure):
     _fields_ = [("hidden_size", C.c_int32), ("num_filters", C.c_int32), ("num_residual_layers", C.c_int32),
                 ("n_ratios", C.c_int32), ("ratios", C.c_int32 * 8), ("kernel_size", C.c_int32), ("last_kernel_size", C.c_int32),
@@ -71,7 +80,8 @@ class TalkerStatsC(C.Structure):
                 ("attn_nsplit_last", C.c_int32), ("attn_span_last", C.c_int32), ("cp_fused_per_step", C.c_int32),
                 ("cp_fused_launches_last", C.c_int64), ("cp_fused_giveups", C.c_int32), ("cp_fused_capacity", C.c_int32),
                 ("cp_fused_active", C.c_int32), ("cp_mlp_per_step", C.c_int32), ("cp_layer_per_step", C.c_int32),
-                ("ks_split_per_step", C.c_int32), ("attn_gq_per_step", C.c_int32)]
+                ("ks_split_per_step", C.c_int32), ("attn_gq_per_step", C.c_int32),
+                ("row_table_last", C.c_int32), ("graph_captures", C.c_int64)]
 
 
 class CodecStatsC(C.Structure):
@@ -83,7 +93,7 @@ class GemmClassC(C.Structure):
                 ("min_us", C.c_double), ("max_us", C.c_double), ("bytes_per_launch", C.c_double)]
 
 
-ABI_VERSION = 13          # include/qtts.h; bumped on any signature change
+ABI_VERSION = 14          # include/qtts.h; bumped on any signature change
 
 # every symbol include/qtts.h declares (checked by tests/test_host_logic.py::test_abi_exports_every_declared_symbol without a GPU)
 SYMBOLS = ["qtts_last_error", "qtts_abi_version", "qtts_set_option", "qtts_get_option", "qtts_codec_create", "qtts_codec_destroy", "qtts_codec_bind",
@@ -96,6 +106,7 @@ SYMBOLS = ["qtts_last_error", "qtts_abi_version", "qtts_set_option", "qtts_get_o
            "qtts_talker_create", "qtts_talker_destroy", "qtts_talker_bind", "qtts_talker_finalize",
            "qtts_talker_text_projection", "qtts_talker_text_embed", "qtts_talker_assemble_rows", "qtts_talker_prefill",
            "qtts_talker_generate", "qtts_talker_stream_begin", "qtts_talker_stream_step", "qtts_talker_stream_end",
+           "qtts_talker_generate_rows", "qtts_talker_stream_begin_rows",
            "qtts_talker_debug_logits", "qtts_talker_debug_cp_logits", "qtts_talker_get_stats", "qtts_talker_get_gemm_profile", "qtts_talker_set_teacher",
            "qtts_talker_set_profile"]
 
@@ -179,6 +190,9 @@ def load_library():
     lib.qtts_talker_generate.argtypes = [vp, C.POINTER(SamplingC), i32, i32, i32, C.POINTER(C.c_int32), i32, vp, vp,
                                          vp, C.POINTER(C.c_int32), vp]
     lib.qtts_talker_stream_begin.argtypes = [vp, C.POINTER(SamplingC), i32, i32, i32, C.POINTER(C.c_int32), i32, vp, vp, vp]
+    lib.qtts_talker_generate_rows.argtypes = [vp, C.POINTER(RowSamplingC), i32, i32, C.POINTER(C.c_int32), i32, vp, vp, vp,
+                                              C.POINTER(C.c_int32), vp]
+    lib.qtts_talker_stream_begin_rows.argtypes = [vp, C.POINTER(RowSamplingC), i32, i32, C.POINTER(C.c_int32), i32, vp, vp, vp]
     lib.qtts_talker_stream_step.argtypes = [vp, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp]
     lib.qtts_talker_stream_end.argtypes = [vp, vp, C.POINTER(C.c_int32), vp]
     lib.qtts_talker_debug_logits.argtypes = [vp, f32p, vp]

@@ -338,8 +338,22 @@ void launch_cp_layer(const CpLayerParams& P, hipStream_t st);
 void cp_layer_set_launch_events(hipEvent_t start, hipEvent_t stop);
 
 // --------------------------------------------------------------------------------- sampling.hip
+// One request's sampling settings (qtts_row_sampling, include/qtts.h) as the samplers read them from device memory: 64 bytes, so that
+// entry b is one aligned block.  A launch reads the talker half or the subtalker half (SampleParams::rows_sub).
+struct SampleRow {
+    int do_sample; int top_k; float top_p; float temperature;                   // words 0..3: the talker's sampler
+    int sub_do_sample; int sub_top_k; float sub_top_p; float sub_temperature;   // words 4..7: the code predictor's samplers
+    float repetition_penalty; int max_new_tokens; int min_new_tokens; int pad0; // words 8..11: talker only
+    unsigned long long seed;
+    int pad1, pad2;
+};
+static_assert(offsetof(SampleRow, sub_do_sample) == 16 && offsetof(SampleRow, repetition_penalty) == 32 && offsetof(SampleRow, seed) == 48,
+              "sampling.hip: row_knobs reads an entry as 16-byte blocks");
+static_assert(sizeof(SampleRow) == 64, "SampleRow is padded to a power of two");
+
 struct SampleParams {
-    const float* logits; int ld; int V; int B;
+    const float* logits; int ld; int V; int B;   // `logits`: 16-byte aligned, >= 48 bytes (row_knobs reads its first three 16-byte
+                                                 // blocks, and drops them, in every launch without a table)
     // processors
     const int* generated; int gen_stride;   // [B][gen_stride] tokens so far (talker) or null
     const int* n_generated_dev;              // device count of tokens generated so far (or null -> 0)
@@ -365,6 +379,12 @@ struct SampleParams {
     const float* gather_emb; int gather_C; float* gather_out; unsigned short* gather_out16;
     // A/B variant (build.py VARIANTS): second fused gather -- the next pass's layer-0 q|k|v row, tabulated at finalize
     const float* gather2_emb; int gather2_C; float* gather2_out;
+    // per-row settings (qtts_talker_generate_rows): when set, every knob above that a request may choose -- do_sample, top_k, top_p,
+    // temperature, repetition_penalty, min_new_tokens, the Philox key -- and the row's own max_new_tokens come from rows[b]; the
+    // Philox counter is then (step, 0, stream_id, 0), so a row's draws do not depend on its place in the batch.
+    const SampleRow* rows = nullptr;         // [B] device
+    int rows_sub = 0;                        // 1: this launch reads the subtalker half of an entry (code predictor)
+    int rows_fast = 0;                       // host's verdict over the whole table: every row meets sample_kernel_v2's predicate
 };
 void launch_sample(const SampleParams& p, hipStream_t st);
 

@@ -5,7 +5,8 @@
 // [Temperature -> TopK] -> argmax | softmax + multinomial.  argmax breaks ties towards the lowest
 // index (torch.argmax).  Sampling draws from a counter-based Philox4x32-10 stream keyed by
 // (seed; step, row, codebook) -- torch's global RNG stream is not reproducible across devices, so
-// sampled runs are compared distributionally, greedy runs bit-exactly.
+// sampled runs are compared distributionally, greedy runs bit-exactly.  With a per-row settings table (SampleParams::rows) the key is
+// the ROW's seed and the counter (step, 0, codebook): a request's draws are a function of its own seed, not of its place in a batch.
 #include "common.h"
 #include "kernels.h"
 #include "tstamp.h"
@@ -36,6 +37,53 @@ __device__ inline uint32_t float_key(float f) {  // monotone float -> uint (larg
 
 constexpr int SAMPLE_MAX_V = 8192;
 constexpr int CAND_MAX = 1024;          // top-k candidates (scores >= the k-th largest per-thread max) ranked exactly in LDS
+
+// The knobs of one row of a launch: the launch constants, or -- table mode -- entry b of the per-row table (one 64-byte block, uniform
+// across the workgroup).  `limit`: the row's own max_new_tokens (table mode; otherwise no row limit: sample_finish_kernel stops the call).
+struct RowKnobs {
+    int do_sample, top_k, min_new, limit;
+    float top_p, temperature, rep;
+    unsigned long long seed;
+    uint32_t ctr_row;                  // second word of the Philox counter: the row index, or 0 in table mode
+};
+__device__ __forceinline__ RowKnobs row_knobs(const SampleParams& p, int b) {
+    // An entry is four 16-byte blocks: the talker's knobs | the subtalker's knobs | {rep, max_new, min_new, -} | {seed, -}; a launch
+    // reads its half's block and the last two.  The requests are made UNCONDITIONALLY and the choice between table and launch constants
+    // is made on VALUES.  Without a table (the scalar path) they read the first 48 bytes at the BASE of `p.logits` -- row 0's, whatever b
+    // is: a line the launch requests anyway -- and the values are dropped; that is why SampleParams asks for `logits` to be 16-byte
+    // aligned and at least 48 bytes long.  Why not `if (p.rows)` around the loads: hipcc (ROCm 7) then folds them with the reads of the
+    // launch constants into one load through a selected ADDRESS, a kernel argument whose address is taken is copied to scratch, and
+    // tests/test_build_static.py::test_no_kernel_spills_or_scratch turns red -- the guard against a compiler that decides otherwise.
+    const bool tab = p.rows != nullptr, sub = p.rows_sub != 0;
+    const uint4* e = tab ? reinterpret_cast<const uint4*>(p.rows + b) : reinterpret_cast<const uint4*>(p.logits);
+    const uint4 w0 = e[sub ? 1 : 0], w2 = e[2];
+    const unsigned long long* sd = tab ? &p.rows[b].seed : (p.seed_dev ? p.seed_dev : reinterpret_cast<const unsigned long long*>(p.logits));
+    const unsigned long long seed_mem = *sd;
+    RowKnobs k;
+    k.do_sample = tab ? (int)w0.x : p.do_sample;
+    k.top_k = tab ? (int)w0.y : p.top_k;
+    k.top_p = tab ? __uint_as_float(w0.z) : p.top_p;
+    k.temperature = tab ? __uint_as_float(w0.w) : p.temperature;
+    k.rep = tab ? (sub ? 1.0f : __uint_as_float(w2.x)) : p.repetition_penalty;
+    k.min_new = tab ? (int)w2.z : p.min_new_tokens;
+    k.limit = tab ? (int)w2.y : 0x7fffffff;
+    k.seed = (tab || p.seed_dev) ? seed_mem : p.seed;
+    k.ctr_row = tab ? 0u : (uint32_t)b;
+    return k;
+}
+// The talker's bookkeeping of one sampled token (thread 0): finished rows keep receiving pad (= eos); a row that has reached its own
+// max_new_tokens (table mode) is treated exactly like a row that hit EOS -- token index limit - 1 and everything after it is eos, so
+// the row's frames before the first eos are the limit - 1 frames a scalar max_new_tokens of that value yields.
+__device__ __forceinline__ int finish_row(const SampleParams& p, int b, int n_gen, int limit, int token) {
+    if (p.unfinished) {
+        const int uf = p.unfinished[b];
+        if (!uf || n_gen >= limit - 1) token = p.eos;
+        p.unfinished[b] = uf && (token != p.eos);
+        if (p.generated_out) p.generated_out[(size_t)b * p.gen_stride + n_gen] = token;
+    }
+    p.tok_out[(size_t)b * p.tok_stride] = token;
+    return token;
+}
 
 // The next pass's input rows (tabulated projected embedding, tabulated layer-0 q|k|v) are random rows of 117 / 470 MB tables:
 // every request is an HBM round trip (~1 us), so ALL of a thread's requests are issued before the first store -- the round-1
@@ -101,17 +149,18 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleParams p) {
     const int V = p.V;
     const float* lg = p.logits + (size_t)b * p.ld;
     const int n_gen = p.n_generated_dev ? *p.n_generated_dev : 0;
+    const RowKnobs kn = row_knobs(p, b);
     for (int v = tid; v < V; v += 256) sc[v] = lg[v];
     __syncthreads();
-    if (p.generated && p.repetition_penalty != 1.0f) {
+    if (p.generated && kn.rep != 1.0f) {
         for (int i = tid; i < n_gen; i += 256) {
             const int tok = p.generated[(size_t)b * p.gen_stride + i];
             const float s = lg[tok];
-            sc[tok] = s < 0.f ? s * p.repetition_penalty : s / p.repetition_penalty;  // same value for duplicates
+            sc[tok] = s < 0.f ? s * kn.rep : s / kn.rep;  // same value for duplicates
         }
         __syncthreads();
     }
-    if (p.eos >= 0 && n_gen < p.min_new_tokens && tid == 0) sc[p.eos] = -INFINITY;
+    if (p.eos >= 0 && n_gen < kn.min_new && tid == 0) sc[p.eos] = -INFINITY;
     __syncthreads();
     if (p.suppress_mask) {
         for (int v = tid; v < V; v += 256)
@@ -120,7 +169,7 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleParams p) {
     }
 
     int token = 0;
-    if (!p.do_sample) {
+    if (!kn.do_sample) {
         float bv = -INFINITY;
         int bi = 0x7fffffff;
         for (int v = tid; v < V; v += 256) {
@@ -140,18 +189,17 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleParams p) {
             if (fred[w] > bv || (fred[w] == bv && ired[w] < bi)) { bv = fred[w]; bi = ired[w]; }
         token = bi;
     } else {
-        if (p.temperature != 1.0f) {
-            for (int v = tid; v < V; v += 256) sc[v] = sc[v] / p.temperature;
+        if (kn.temperature != 1.0f) {
+            for (int v = tid; v < V; v += 256) sc[v] = sc[v] / kn.temperature;
             __syncthreads();
         }
         const uint32_t step = p.step_dev ? (uint32_t)*p.step_dev : 0u;
         uint32_t rnd[4];
-        const unsigned long long seed = p.seed_dev ? *p.seed_dev : p.seed;
-        philox4x32_10(step, (uint32_t)b, p.stream_id, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), rnd);
+        philox4x32_10(step, kn.ctr_row, p.stream_id, 0u, (uint32_t)kn.seed, (uint32_t)(kn.seed >> 32), rnd);
         const float u = (float)(rnd[0] >> 8) * (1.0f / 16777216.0f);
         bool sampled = false;
-        bool need_search = p.top_k > 0 && p.top_k < V;
-        if (need_search && p.top_k <= 256) {
+        bool need_search = kn.top_k > 0 && kn.top_k < V;
+        if (need_search && kn.top_k <= 256) {
             // ---- fast top-k: the k-th largest score is >= the k-th largest PER-THREAD maximum, so only scores at or
             // above that bound can be in the top-k.  Compact those few candidates and rank them exactly.
             float tm = -INFINITY;
@@ -169,7 +217,7 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleParams p) {
                     rank += (k4.z > mk) || (k4.z == mk && j + 2 < tid);
                     rank += (k4.w > mk) || (k4.w == mk && j + 3 < tid);
                 }
-                if (rank == p.top_k - 1) pick_hi = (int)mk;     // lower bound T0 (as a key)
+                if (rank == kn.top_k - 1) pick_hi = (int)mk;     // lower bound T0 (as a key)
             }
             __syncthreads();
             const uint32_t T0 = (uint32_t)pick_hi;
@@ -204,7 +252,7 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleParams p) {
                         rank += (k4.z > mk) || (k4.z == mk && j + 2 < i);
                         rank += (k4.w > mk) || (k4.w == mk && j + 3 < i);
                     }
-                    if (rank == p.top_k - 1) pick_lo = (int)mk;  // key of the k-th largest score
+                    if (rank == kn.top_k - 1) pick_lo = (int)mk;  // key of the k-th largest score
                 }
                 __syncthreads();
                 const uint32_t thr = (uint32_t)pick_lo;          // HF TopK keeps every score >= it (ties included)
@@ -222,7 +270,7 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleParams p) {
                     }
 #pragma unroll
                     for (int o = 32; o > 0; o >>= 1) tot += __shfl_xor(tot, o);
-                    if (p.top_p < 1.0f) {
+                    if (kn.top_p < 1.0f) {
                         // HF TopPLogitsWarper after TopK: ascending cumulative softmax <= 1 - top_p is removed, i.e. a token
                         // stays iff the probability mass of everything ranked strictly above it is < top_p (the top token
                         // always stays).  Ranks are exact (value desc, slot asc); all-pairs over the <= CAND_MAX candidates.
@@ -239,7 +287,7 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleParams p) {
                                     const uint32_t kj = ckey[j];
                                     if (kj > mk || (kj == mk && j < i)) above += cval[j];
                                 }
-                                if (above < p.top_p * tot) keep_e[q] = cval[i];
+                                if (above < kn.top_p * tot) keep_e[q] = cval[i];
                             }
                             tot2 += keep_e[q];
                         }
@@ -287,7 +335,7 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleParams p) {
                 if (lane == 0) ired[(bit & 1) * 4 + wave] = cnt;
                 __syncthreads();
                 const int* r4 = ired + (bit & 1) * 4;
-                if (r4[0] + r4[1] + r4[2] + r4[3] >= p.top_k) prefix = cand;
+                if (r4[0] + r4[1] + r4[2] + r4[3] >= kn.top_k) prefix = cand;
             }
             __syncthreads();
             for (int v = tid; v < V; v += 256)
@@ -312,7 +360,7 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleParams p) {
                 sc[v] = e;
                 mine += e;
             }
-            if (p.top_p < 1.0f) {
+            if (kn.top_p < 1.0f) {
                 // ---- general top-p (HF TopPLogitsWarper, IM:287-352 forwards any top_p): with no top-k bound, or one beyond the
                 // candidate buffers above, the nucleus is cut on the whole vocabulary.  A token stays iff the softmax mass of everything
                 // ranked strictly above it is < top_p (ascending cumulative probability > 1 - top_p; the top token always stays), so
@@ -327,7 +375,7 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleParams p) {
                     return (pred[slot * 4 + 0] + pred[slot * 4 + 1]) + (pred[slot * 4 + 2] + pred[slot * 4 + 3]);
                 };
                 const float total0 = block_sum(mine, 0);
-                const float P = p.top_p * total0;
+                const float P = kn.top_p * total0;
                 uint32_t cut = 0u;                           // largest key with S(key) >= P found so far
                 bool any_cut = false;
                 for (int bit = 31; bit >= 0; --bit) {
@@ -372,15 +420,7 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleParams p) {
 
     if (token < 0 || token >= V) token = 0;   // all-NaN logits must not turn into an out-of-range gather index
     gather_next_rows(p, token, b, tid);        // every thread holds the same token (block-uniform by construction)
-    if (tid == 0) {
-        if (p.unfinished) {
-            const int uf = p.unfinished[b];
-            if (!uf) token = p.eos;                        // finished rows keep receiving pad (= eos)
-            p.unfinished[b] = uf && (token != p.eos);
-            if (p.generated_out) p.generated_out[(size_t)b * p.gen_stride + n_gen] = token;
-        }
-        p.tok_out[(size_t)b * p.tok_stride] = token;
-    }
+    if (tid == 0) finish_row(p, b, n_gen, kn.limit, token);
 }
 
 // Wave-level tail of the top-k sampler (round 2, second pass -- the in-kernel timestamps of profiles/r02_tstamp_frame.md showed
@@ -464,7 +504,7 @@ __global__ __launch_bounds__(256) void sample_kernel_v2(SampleParams p) {
     const int done = p.done_in ? *p.done_in : 0;
     const int n_gen = p.n_generated_dev ? *p.n_generated_dev : 0;
     const uint32_t step = p.step_dev ? (uint32_t)*p.step_dev : 0u;
-    const unsigned long long seed = p.seed_dev ? *p.seed_dev : p.seed;
+    const RowKnobs kn = row_knobs(p, b);       // (table mode: the row's 64-byte entry, requested here with everything else)
     // the first 256 entries of this row's token history (repetition penalty; the talker's call only) are requested here, before the
     // count is known: behind the flag-clearing barrier below the load was a memory round trip of its own (2-6 us by box)
     const int* gsrc = p.generated ? p.generated + (size_t)b * p.gen_stride + (tid < p.gen_stride ? tid : 0) : reinterpret_cast<const int*>(lg);
@@ -480,7 +520,7 @@ __global__ __launch_bounds__(256) void sample_kernel_v2(SampleParams p) {
     if (done) return;
     QTTS_TS_DRAINED(1);                    // (tstamp build: phases 1..5 = logits arrived | bound | candidates ranked | drawn | rows gathered)
     // ---- 1. HF processors, in HF's order, on this thread's own logits
-    if (p.generated && p.repetition_penalty != 1.0f) {       // scatter -> presence flags in LDS (idempotent for duplicates)
+    if (p.generated && kn.rep != 1.0f) {       // scatter -> presence flags in LDS (idempotent for duplicates)
 #pragma unroll
         for (int it = 0; it < EPT; ++it) sc[it * 256 + tid] = 0.f;
         __syncthreads();
@@ -492,21 +532,21 @@ __global__ __launch_bounds__(256) void sample_kernel_v2(SampleParams p) {
         __syncthreads();
 #pragma unroll
         for (int it = 0; it < EPT; ++it)
-            if (sc[it * 256 + tid] != 0.f) x[it] = x[it] < 0.f ? x[it] * p.repetition_penalty : x[it] / p.repetition_penalty;
+            if (sc[it * 256 + tid] != 0.f) x[it] = x[it] < 0.f ? x[it] * kn.rep : x[it] / kn.rep;
         __syncthreads();                                     // flags consumed before the scores overwrite them
     }
-    const bool block_eos = p.eos >= 0 && n_gen < p.min_new_tokens;
+    const bool block_eos = p.eos >= 0 && n_gen < kn.min_new;
     float tm = -INFINITY;
 #pragma unroll
     for (int it = 0; it < EPT; ++it) {
         const int v = it * 256 + tid;
         if ((block_eos && v == p.eos) || sup[it]) x[it] = -INFINITY;
-        if (p.temperature != 1.0f) x[it] = x[it] / p.temperature;
+        if (kn.temperature != 1.0f) x[it] = x[it] / kn.temperature;
         sc[v] = x[it];                                       // for the general fallback paths only
         if (v < V) tm = fmaxf(tm, x[it]);
     }
     uint32_t rnd[4];
-    philox4x32_10(step, (uint32_t)b, p.stream_id, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), rnd);
+    philox4x32_10(step, kn.ctr_row, p.stream_id, 0u, (uint32_t)kn.seed, (uint32_t)(kn.seed >> 32), rnd);
     const float u = (float)(rnd[0] >> 8) * (1.0f / 16777216.0f);
     // ---- 2. candidate bound: k-th largest of the 64 quad maxima (<= the k-th largest score), ranked by every wave itself
     tm = fmaxf(tm, __shfl_xor(tm, 1));
@@ -523,7 +563,7 @@ __global__ __launch_bounds__(256) void sample_kernel_v2(SampleParams p) {
         for (int lo = 30; lo >= 0; lo -= 2) {                  // two bits per round (see topk_softmax_wave)
             const uint32_t c1 = T0 | (1u << lo), c2 = T0 | (2u << lo), c3 = T0 | (3u << lo);
             const int n1 = __popcll(__ballot(mk >= c1)), n2 = __popcll(__ballot(mk >= c2)), n3 = __popcll(__ballot(mk >= c3));
-            T0 = n3 >= p.top_k ? c3 : (n2 >= p.top_k ? c2 : (n1 >= p.top_k ? c1 : T0));
+            T0 = n3 >= kn.top_k ? c3 : (n2 >= kn.top_k ? c2 : (n1 >= kn.top_k ? c1 : T0));
         }
     }
     // ---- 3. compaction in sample_kernel's slot order (wave, slice, lane)
@@ -556,9 +596,9 @@ __global__ __launch_bounds__(256) void sample_kernel_v2(SampleParams p) {
         __syncthreads();
         QTTS_TS(3);
         if (wave == 0) {       // exact top-k threshold, softmax over the survivors and the inverse-CDF draw: one wave, no barrier
-            float tot = n_c <= 128 ? topk_softmax_wave<2>(n_c, p.top_k, lane, cval, ckey)      // (typical: ~1.7 k candidates)
-                                   : topk_softmax_wave<CAND_MAX / 64>(n_c, p.top_k, lane, cval, ckey);
-            if (p.top_p < 1.0f) {
+            float tot = n_c <= 128 ? topk_softmax_wave<2>(n_c, kn.top_k, lane, cval, ckey)      // (typical: ~1.7 k candidates)
+                                   : topk_softmax_wave<CAND_MAX / 64>(n_c, kn.top_k, lane, cval, ckey);
+            if (kn.top_p < 1.0f) {
                 float keep_e[CAND_MAX / 64];
                 float tot2 = 0.f;
 #pragma unroll
@@ -572,7 +612,7 @@ __global__ __launch_bounds__(256) void sample_kernel_v2(SampleParams p) {
                             const uint32_t kj = ckey[j];
                             if (kj > mk || (kj == mk && j < i)) above += cval[j];
                         }
-                        if (above < p.top_p * tot) keep_e[q] = cval[i];
+                        if (above < kn.top_p * tot) keep_e[q] = cval[i];
                     }
                     tot2 += keep_e[q];
                 }
@@ -616,7 +656,7 @@ __global__ __launch_bounds__(256) void sample_kernel_v2(SampleParams p) {
             if (lane == 0) ired[(bit & 1) * 4 + wave] = cnt;
             __syncthreads();
             const int* r4 = ired + (bit & 1) * 4;
-            if (r4[0] + r4[1] + r4[2] + r4[3] >= p.top_k) prefix = cand;
+            if (r4[0] + r4[1] + r4[2] + r4[3] >= kn.top_k) prefix = cand;
         }
         __syncthreads();
         for (int v = tid; v < V; v += 256)
@@ -664,15 +704,7 @@ __global__ __launch_bounds__(256) void sample_kernel_v2(SampleParams p) {
 
     if (token < 0 || token >= V) token = 0;
     gather_next_rows(p, token, b, tid);
-    if (tid == 0) {
-        if (p.unfinished) {
-            const int uf = p.unfinished[b];
-            if (!uf) token = p.eos;
-            p.unfinished[b] = uf && (token != p.eos);
-            if (p.generated_out) p.generated_out[(size_t)b * p.gen_stride + n_gen] = token;
-        }
-        p.tok_out[(size_t)b * p.tok_stride] = token;
-    }
+    if (tid == 0) finish_row(p, b, n_gen, kn.limit, token);
     QTTS_TS_DRAINED(5);
     QTTS_TS_END(sample, 3, V, 0);
 }
@@ -683,8 +715,11 @@ __global__ __launch_bounds__(256) void sample_kernel_v2(SampleParams p) {
 // three barriers; deleted.)
 void launch_sample(const SampleParams& p, hipStream_t st) {
     QTTS_REQUIRE(p.V <= SAMPLE_MAX_V, QTTS_ERR_LIMIT, "sample: vocab too large");
-    QTTS_REQUIRE(!(p.do_sample && p.top_p < 1.0f) || p.top_p > 0.0f, QTTS_ERR_ARG, "sample: top_p must be in (0, 1]");
-    if (p.do_sample && p.top_k > 0 && p.top_k <= 64 && p.top_k < p.V && p.V <= 4096) {
+    QTTS_REQUIRE(p.rows || !(p.do_sample && p.top_p < 1.0f) || p.top_p > 0.0f, QTTS_ERR_ARG, "sample: top_p must be in (0, 1]");
+    // table mode: the host has looked at every row of the table before uploading it (rows_fast: all of them meet the predicate below);
+    // otherwise the general kernel runs, which takes greedy rows, top-p-only rows and any top-k.  The kernel never re-dispatches.
+    const bool fast = p.rows ? (p.rows_fast && p.V <= 4096) : (p.do_sample && p.top_k > 0 && p.top_k <= 64 && p.top_k < p.V && p.V <= 4096);
+    if (fast) {
         if (p.V <= 2048) hipLaunchKernelGGL(sample_kernel_v2<8>, dim3(p.B), dim3(256), 0, st, p);
         else if (p.V <= 3072) hipLaunchKernelGGL(sample_kernel_v2<12>, dim3(p.B), dim3(256), 0, st, p);
         else hipLaunchKernelGGL(sample_kernel_v2<16>, dim3(p.B), dim3(256), 0, st, p);

@@ -77,14 +77,34 @@ struct qtts_talker {
     hipGraphExec_t graph_exec = nullptr;
     // everything a captured frame step bakes into its kernel arguments and that can differ between generate() calls;
     // the graph is re-captured only when this changes (the Philox seed lives in device memory for the same reason)
+    // With a per-row settings table (qtts_talker_generate_rows) the samplers read every knob from device memory, so the key holds no
+    // sampling value: only which kernel class each of the two sampler stacks runs (row_fast_t / row_fast_c), the largest limit and eos.
     struct GraphKey {
         int B, Tt, eos, min_new, max_new, max_frames;
         int do_sample, top_k, sub_do_sample, sub_top_k;
         float top_p, temperature, rep, sub_top_p, sub_temperature;
         const void *codes, *hidden, *trailing, *tts_pad, *generated;
+        int row_mode, row_fast_t, row_fast_c;
         bool operator==(const GraphKey& o) const { return memcmp(this, &o, sizeof(GraphKey)) == 0; }
     } graph_key;
+    GraphKey make_key(const qtts_sampling& sp, int eos, int min_new, int max_new, int max_frames, const void* codes, const void* hidden) const {
+        GraphKey key;
+        memset(&key, 0, sizeof(key));          // (padding bytes take part in the comparison)
+        key.B = B; key.Tt = Tt; key.eos = eos; key.max_new = max_new; key.max_frames = max_frames;
+        if (row_mode) { key.row_mode = 1; key.row_fast_t = row_fast_t; key.row_fast_c = row_fast_c; }
+        else {
+            key.min_new = min_new; key.do_sample = sp.do_sample; key.top_k = sp.top_k; key.sub_do_sample = sp.subtalker_dosample;
+            key.sub_top_k = sp.subtalker_top_k; key.top_p = sp.top_p; key.temperature = sp.temperature; key.rep = sp.repetition_penalty;
+            key.sub_top_p = sp.subtalker_top_p; key.sub_temperature = sp.subtalker_temperature;
+        }
+        key.codes = codes; key.hidden = hidden; key.trailing = trailing.p; key.tts_pad = tts_pad.p; key.generated = generated.p;
+        return key;
+    }
     DevBuf seed_d;
+    // per-row settings (qtts_talker_generate_rows / stream_begin_rows): max_batch entries, uploaded per call like seed_d
+    DevBuf rows_d;
+    bool row_mode = false, row_fast_t = false, row_fast_c = false;
+    int64_t graph_captures = 0;        // frame-graph captures over the engine's life
     // resumable generation (qtts_talker_stream_*): everything a later call needs to keep stepping the same request
     struct StreamGen {
         bool active = false;
@@ -564,6 +584,7 @@ struct qtts_talker {
                 throw;
             }
             QTTS_CHECK_HIP(hipStreamEndCapture(st, &g));
+            ++graph_captures;
             size_t nn = 0;
             QTTS_CHECK_HIP(hipGraphGetNodes(g, nullptr, &nn));
             graph_nodes = (int)nn;
@@ -877,7 +898,7 @@ void qtts_talker::finalize() {
         cp_hid.alloc((size_t)CP_HID_SLOTS * 8 * (bf16 ? cd.H / 2 : cd.H) * 8);
         QTTS_CHECK_HIP(hipMemset(cp_hid.p, 0, cp_hid.bytes));
     }
-    n_pad_d.alloc(R * 4); suppress.alloc(c.vocab_size); seed_d.alloc(8);
+    n_pad_d.alloc(R * 4); suppress.alloc(c.vocab_size); seed_d.alloc(8); rows_d.alloc((size_t)R * sizeof(SampleRow));
     QTTS_CHECK_HIP(hipMemset(ss_rows.p, 0, ss_rows.bytes));
     int* ip = ints.as<int>();
     ss = {ip + 0, ip + 1, ip + 2, ip + 3, ip + 4, ip + 64, ip + 6};
@@ -999,6 +1020,7 @@ void qtts_talker::sample_talker(const qtts_sampling& sp, int eos, int min_new, i
     p.seed = sp.seed; p.seed_dev = seed_d.as<unsigned long long>(); p.stream_id = 0; p.step_dev = ss.n_generated;
     p.tok_out = cur_tok.as<int>(); p.tok_stride = 1; p.unfinished = ss.unfinished; p.generated_out = generated.as<int>();
     p.max_new_tokens = max_new; p.done_in = ss.done;
+    if (row_mode) { p.rows = rows_d.as<SampleRow>(); p.rows_sub = 0; p.rows_fast = row_fast_t; }
     if (tf.codes && tf.trace) launch_teacher(teacher_params(), 0, st);
     launch_sample(p, st);
     launch_sample_finish(ss, B, max_new, st);
@@ -1059,6 +1081,7 @@ void qtts_talker::frame_step(const qtts_sampling& sp, int eos, int min_new, int 
         s.top_p = sp.subtalker_top_p; s.temperature = sp.subtalker_temperature; s.seed = sp.seed; s.stream_id = 1 + j;
         s.seed_dev = seed_d.as<unsigned long long>();
         s.step_dev = ss.n_generated; s.tok_out = sub.as<int>() + j; s.tok_stride = G; s.done_in = ss.done;
+        if (row_mode) { s.rows = rows_d.as<SampleRow>(); s.rows_sub = 1; s.rows_fast = row_fast_c; }
         if (j + 1 < G - 1) {       // next pass's input = codec_embedding[j](this token) (M:1281)
             s.gather_emb = emb_cp.as<float>() + (size_t)j * c.cp_vocab_size * td.H; s.gather_C = td.H;
             s.gather_out = has_proj ? cp_in.as<float>() : cp_x.as<float>();
@@ -1235,34 +1258,78 @@ int qtts_talker_prefill(qtts_talker* t, const float* embeds_dev, int32_t B, int3
     QTTS_API_END
 }
 
-int qtts_talker_generate(qtts_talker* t, const qtts_sampling* sp, int32_t max_new_tokens, int32_t min_new_tokens,
-                         int32_t eos_token_id, const int32_t* suppress_host, int32_t n_suppress, int64_t* codes_dev,
-                         float* hidden_dev, int64_t* tokens_dev, int32_t* n_frames_host, void* stream) {
-    QTTS_API_BEGIN
-    QTTS_REQUIRE(t && sp && codes_dev && n_frames_host, QTTS_ERR_ARG, "null argument");
-    QTTS_REQUIRE(t->prefilled, QTTS_ERR_STATE, "generate: prefill() first");
-    QTTS_REQUIRE(max_new_tokens >= 1, QTTS_ERR_ARG, "max_new_tokens >= 1");
-    QTTS_REQUIRE(t->T0 + max_new_tokens <= t->cfg.max_seq, QTTS_ERR_LIMIT, "prompt + max_new_tokens exceeds max_seq");
-    QTTS_REQUIRE(eos_token_id >= 0 && eos_token_id < t->cfg.vocab_size, QTTS_ERR_ARG, "eos_token_id");
-    hipStream_t st = (hipStream_t)stream;
-    const int B = t->B, V = t->cfg.vocab_size;
-    if (t->tf.codes)
-        QTTS_REQUIRE(min_new_tokens >= max_new_tokens && t->tf.F == max_new_tokens - 1 && !sp->do_sample && !sp->subtalker_dosample,
-                     QTTS_ERR_ARG, "teacher forcing: greedy, min_new_tokens == max_new_tokens == forced frames + 1");
-    t->prefilled = false;  // the KV cache / loop state are consumed by this call
-    {
-        std::vector<unsigned char> m(V, 0);
-        for (int i = 0; i < n_suppress; ++i) {
-            QTTS_REQUIRE(suppress_host[i] >= 0 && suppress_host[i] < V, QTTS_ERR_ARG, "suppress token out of range");
-            m[suppress_host[i]] = 1;
-        }
-        QTTS_CHECK_HIP(hipMemcpyAsync(t->suppress.p, m.data(), V, hipMemcpyHostToDevice, st));
-        const unsigned long long seed = sp->seed;
-        QTTS_CHECK_HIP(hipMemcpyAsync(t->seed_d.p, &seed, 8, hipMemcpyHostToDevice, st));
-        QTTS_CHECK_HIP(hipStreamSynchronize(st));
+}   // extern "C"
+
+// ---- per-row settings (qtts_talker_generate_rows / qtts_talker_stream_begin_rows): the table as the samplers read it, and what the
+// host loop needs from it.  Everything is checked here, before the call consumes the prefill.
+struct RowTable {
+    std::vector<SampleRow> tab;
+    int max_new = 0;            // the largest limit: buffer sizes, the stop latch, the frame count's bound
+    int poll_from = 0x7fffffff; // no row can finish before this many tokens exist (EOS blocked and limit not reached): no poll needed earlier
+    bool fast_t = true, fast_c = true;      // every row meets sample_kernel_v2's predicate, talker / subtalker half (launch_sample)
+};
+static RowTable check_rows(const qtts_talker* t, const qtts_row_sampling* rows, int n_rows, const char* who) {
+    auto fail = [&](int code, int b, const char* what) { throw Error(code, std::string(who) + ": row " + std::to_string(b) + ": " + what); };
+    QTTS_REQUIRE(rows, QTTS_ERR_ARG, "null argument");
+    QTTS_REQUIRE(n_rows == t->B, QTTS_ERR_ARG, std::string(who) + ": n_rows (" + std::to_string(n_rows) + ") must equal the prefilled batch (" +
+                                                   std::to_string(t->B) + ")");
+    QTTS_REQUIRE(!t->tf.codes, QTTS_ERR_ARG, std::string(who) + ": teacher forcing takes scalar settings (qtts_talker_generate), not a per-row table");
+    QTTS_REQUIRE(t->profile != 2, QTTS_ERR_ARG, std::string(who) + ": profile mode 2 takes scalar settings, not a per-row table");
+    RowTable r;
+    r.tab.resize(n_rows);
+    const int V = t->cfg.vocab_size, Vc = t->cfg.cp_vocab_size;
+    for (int b = 0; b < n_rows; ++b) {
+        const qtts_row_sampling& q = rows[b];
+        if (q.max_new_tokens < 1) fail(QTTS_ERR_ARG, b, "max_new_tokens >= 1");
+        if (q.do_sample && !(q.top_p > 0.0f && q.top_p <= 1.0f)) fail(QTTS_ERR_ARG, b, "top_p must be in (0, 1]");
+        if (q.subtalker_dosample && !(q.subtalker_top_p > 0.0f && q.subtalker_top_p <= 1.0f)) fail(QTTS_ERR_ARG, b, "subtalker_top_p must be in (0, 1]");
+        if (!(q.temperature > 0.0f)) fail(QTTS_ERR_ARG, b, "temperature must be > 0");
+        if (!(q.subtalker_temperature > 0.0f)) fail(QTTS_ERR_ARG, b, "subtalker_temperature must be > 0");
+        if (q.top_k < 0 || q.subtalker_top_k < 0) fail(QTTS_ERR_ARG, b, "top_k >= 0");
+        if (!(q.repetition_penalty > 0.0f)) fail(QTTS_ERR_ARG, b, "repetition_penalty must be > 0");
+        SampleRow& o = r.tab[b];
+        memset(&o, 0, sizeof(o));
+        o.do_sample = q.do_sample ? 1 : 0; o.top_k = q.top_k; o.top_p = q.top_p; o.temperature = q.temperature;
+        o.repetition_penalty = q.repetition_penalty; o.sub_do_sample = q.subtalker_dosample ? 1 : 0; o.sub_top_k = q.subtalker_top_k;
+        o.sub_top_p = q.subtalker_top_p; o.sub_temperature = q.subtalker_temperature; o.seed = q.seed;
+        o.max_new_tokens = q.max_new_tokens; o.min_new_tokens = q.min_new_tokens;
+        r.max_new = std::max(r.max_new, (int)q.max_new_tokens);
+        r.poll_from = std::min(r.poll_from, std::min((int)q.min_new_tokens, (int)q.max_new_tokens - 1));
+        r.fast_t = r.fast_t && o.do_sample && o.top_k > 0 && o.top_k <= 64 && o.top_k < V && V <= 4096;
+        r.fast_c = r.fast_c && o.sub_do_sample && o.sub_top_k > 0 && o.sub_top_k <= 64 && o.sub_top_k < Vc && Vc <= 4096;
     }
-    t->gen_cap = max_new_tokens;
-    t->generated.ensure((size_t)B * max_new_tokens * 4);
+    if (t->T0 + r.max_new > t->cfg.max_seq)
+        throw Error(QTTS_ERR_LIMIT, std::string(who) + ": prompt + the largest max_new_tokens of the table (" + std::to_string(r.max_new) + ") exceeds max_seq");
+    return r;
+}
+// What every generation call does before its first sample: the suppress mask and the Philox key -- or the table -- go to the device,
+// the token history is sized.  Consumes the prefill.
+static void upload_call_state(qtts_talker* t, const qtts_sampling& sp, const RowTable* rt, int max_new, const int32_t* suppress_host, int n_suppress,
+                              hipStream_t st) {
+    const int V = t->cfg.vocab_size;
+    t->prefilled = false;  // the KV cache / loop state are consumed by this call (also when the suppress list below is refused)
+    std::vector<unsigned char> m(V, 0);
+    for (int i = 0; i < n_suppress; ++i) {
+        QTTS_REQUIRE(suppress_host[i] >= 0 && suppress_host[i] < V, QTTS_ERR_ARG, "suppress token out of range");
+        m[suppress_host[i]] = 1;
+    }
+    t->row_mode = rt != nullptr; t->row_fast_t = rt && rt->fast_t; t->row_fast_c = rt && rt->fast_c;
+    QTTS_CHECK_HIP(hipMemcpyAsync(t->suppress.p, m.data(), V, hipMemcpyHostToDevice, st));
+    const unsigned long long seed = sp.seed;
+    QTTS_CHECK_HIP(hipMemcpyAsync(t->seed_d.p, &seed, 8, hipMemcpyHostToDevice, st));
+    if (rt) QTTS_CHECK_HIP(hipMemcpyAsync(t->rows_d.p, rt->tab.data(), rt->tab.size() * sizeof(SampleRow), hipMemcpyHostToDevice, st));
+    QTTS_CHECK_HIP(hipStreamSynchronize(st));
+    t->gen_cap = max_new;
+    t->generated.ensure((size_t)t->B * max_new * 4);
+}
+
+// The body of qtts_talker_generate and qtts_talker_generate_rows.  `rt` set: table mode -- `spv` is unused by the kernels, max_new_tokens
+// is the table's largest limit and min_new_tokens only tells the loop from when on the stop condition can latch.
+static void generate_body(qtts_talker* t, const qtts_sampling* sp, const RowTable* rt, int32_t max_new_tokens, int32_t min_new_tokens,
+                          int32_t eos_token_id, const int32_t* suppress_host, int32_t n_suppress, int64_t* codes_dev,
+                          float* hidden_dev, int64_t* tokens_dev, int32_t* n_frames_host, hipStream_t st) {
+    const int B = t->B;
+    upload_call_state(t, *sp, rt, max_new_tokens, suppress_host, n_suppress, st);
     const int max_frames = std::max(1, max_new_tokens - 1);
     t->frames_run = 0;
     if (!t->profile) { t->prof_ms = 0; t->prof_launches = 0; t->prof_classes.clear(); }
@@ -1278,13 +1345,7 @@ int qtts_talker_generate(qtts_talker* t, const qtts_sampling* sp, int32_t max_ne
     const bool use_graph = t->cfg.use_graph && !t->profile && !t->tf.codes;     // (teacher forcing runs eagerly)
     const int total = max_new_tokens - 1;      // at most this many frame steps
     int f = 0;
-    qtts_talker::GraphKey key;
-    memset(&key, 0, sizeof(key));          // (padding bytes take part in the comparison)
-    key.B = B; key.Tt = t->Tt; key.eos = eos_token_id; key.min_new = min_new_tokens; key.max_new = max_new_tokens;
-    key.max_frames = max_frames; key.do_sample = sp->do_sample; key.top_k = sp->top_k; key.sub_do_sample = sp->subtalker_dosample;
-    key.sub_top_k = sp->subtalker_top_k; key.top_p = sp->top_p; key.temperature = sp->temperature; key.rep = sp->repetition_penalty;
-    key.sub_top_p = sp->subtalker_top_p; key.sub_temperature = sp->subtalker_temperature; key.codes = codes_dev;
-    key.hidden = hidden_dev; key.trailing = t->trailing.p; key.tts_pad = t->tts_pad.p; key.generated = t->generated.p;
+    const qtts_talker::GraphKey key = t->make_key(*sp, eos_token_id, min_new_tokens, max_new_tokens, max_frames, codes_dev, hidden_dev);
     if (!use_graph || !t->any_graph() || !(key == t->graph_key)) { t->destroy_graph(); t->graph_nodes = 0; }
     while (!done && f < total) {
         if (t->profile == 2 && f == 1) {
@@ -1356,6 +1417,38 @@ int qtts_talker_generate(qtts_talker* t, const qtts_sampling* sp, int32_t max_ne
             for (int i = 0; i < fin[4]; ++i) w[(size_t)b * max_new_tokens + i] = h[(size_t)b * max_new_tokens + i];
         copy_on_stream(tokens_dev, w.data(), w.size() * 8, hipMemcpyHostToDevice, st);
     }
+}
+
+extern "C" {
+
+int qtts_talker_generate(qtts_talker* t, const qtts_sampling* sp, int32_t max_new_tokens, int32_t min_new_tokens,
+                         int32_t eos_token_id, const int32_t* suppress_host, int32_t n_suppress, int64_t* codes_dev,
+                         float* hidden_dev, int64_t* tokens_dev, int32_t* n_frames_host, void* stream) {
+    QTTS_API_BEGIN
+    QTTS_REQUIRE(t && sp && codes_dev && n_frames_host, QTTS_ERR_ARG, "null argument");
+    QTTS_REQUIRE(t->prefilled, QTTS_ERR_STATE, "generate: prefill() first");
+    QTTS_REQUIRE(max_new_tokens >= 1, QTTS_ERR_ARG, "max_new_tokens >= 1");
+    QTTS_REQUIRE(t->T0 + max_new_tokens <= t->cfg.max_seq, QTTS_ERR_LIMIT, "prompt + max_new_tokens exceeds max_seq");
+    QTTS_REQUIRE(eos_token_id >= 0 && eos_token_id < t->cfg.vocab_size, QTTS_ERR_ARG, "eos_token_id");
+    if (t->tf.codes)
+        QTTS_REQUIRE(min_new_tokens >= max_new_tokens && t->tf.F == max_new_tokens - 1 && !sp->do_sample && !sp->subtalker_dosample,
+                     QTTS_ERR_ARG, "teacher forcing: greedy, min_new_tokens == max_new_tokens == forced frames + 1");
+    generate_body(t, sp, nullptr, max_new_tokens, min_new_tokens, eos_token_id, suppress_host, n_suppress, codes_dev, hidden_dev, tokens_dev,
+                  n_frames_host, (hipStream_t)stream);
+    QTTS_API_END
+}
+
+int qtts_talker_generate_rows(qtts_talker* t, const qtts_row_sampling* rows_host, int32_t n_rows, int32_t eos_token_id,
+                              const int32_t* suppress_host, int32_t n_suppress, int64_t* codes_dev, float* hidden_dev,
+                              int64_t* tokens_dev, int32_t* n_frames_host, void* stream) {
+    QTTS_API_BEGIN
+    QTTS_REQUIRE(t && rows_host && codes_dev && n_frames_host, QTTS_ERR_ARG, "null argument");
+    QTTS_REQUIRE(t->prefilled, QTTS_ERR_STATE, "generate_rows: prefill() first");
+    QTTS_REQUIRE(eos_token_id >= 0 && eos_token_id < t->cfg.vocab_size, QTTS_ERR_ARG, "eos_token_id");
+    const RowTable rt = check_rows(t, rows_host, n_rows, "generate_rows");
+    const qtts_sampling none{};
+    generate_body(t, &none, &rt, rt.max_new, rt.poll_from, eos_token_id, suppress_host, n_suppress, codes_dev, hidden_dev, tokens_dev,
+                  n_frames_host, (hipStream_t)stream);
     QTTS_API_END
 }
 
@@ -1390,6 +1483,26 @@ static void stream_launch_frames(qtts_talker* t, int n, hipStream_t st) {
     }
 }
 
+// The body of qtts_talker_stream_begin and qtts_talker_stream_begin_rows (`rt`: as in generate_body).
+static void stream_begin_body(qtts_talker* t, const qtts_sampling* sp, const RowTable* rt, int32_t max_new_tokens, int32_t min_new_tokens,
+                              int32_t eos_token_id, const int32_t* suppress_host, int32_t n_suppress, int64_t* codes_dev,
+                              float* hidden_dev, hipStream_t st) {
+    upload_call_state(t, *sp, rt, max_new_tokens, suppress_host, n_suppress, st);
+    auto& g = t->sg;
+    g = qtts_talker::StreamGen{};
+    g.sp = *sp; g.eos = eos_token_id; g.min_new = min_new_tokens; g.max_new = max_new_tokens;
+    g.max_frames = std::max(1, max_new_tokens - 1); g.codes = codes_dev; g.hidden = hidden_dev;
+    t->frames_run = 0;
+    t->sample_talker(*sp, eos_token_id, min_new_tokens, max_new_tokens, st);      // token 0
+    QTTS_CHECK_HIP(hipMemcpyAsync(&g.done, t->ss.done, 4, hipMemcpyDeviceToHost, st));
+    QTTS_CHECK_HIP(hipStreamSynchronize(st));
+    // the cached frame graph is reusable only when everything it baked in is unchanged (as in qtts_talker_generate)
+    const qtts_talker::GraphKey key = t->make_key(*sp, g.eos, g.min_new, g.max_new, g.max_frames, codes_dev, hidden_dev);
+    if (!t->cfg.use_graph || !t->any_graph() || !(key == t->graph_key)) { t->destroy_graph(); t->graph_nodes = 0; }
+    t->graph_key = key;
+    g.active = true;
+}
+
 int qtts_talker_stream_begin(qtts_talker* t, const qtts_sampling* sp, int32_t max_new_tokens, int32_t min_new_tokens,
                              int32_t eos_token_id, const int32_t* suppress_host, int32_t n_suppress, int64_t* codes_dev,
                              float* hidden_dev, void* stream) {
@@ -1401,41 +1514,21 @@ int qtts_talker_stream_begin(qtts_talker* t, const qtts_sampling* sp, int32_t ma
     QTTS_REQUIRE(max_new_tokens >= 1, QTTS_ERR_ARG, "max_new_tokens >= 1");
     QTTS_REQUIRE(t->T0 + max_new_tokens <= t->cfg.max_seq, QTTS_ERR_LIMIT, "prompt + max_new_tokens exceeds max_seq");
     QTTS_REQUIRE(eos_token_id >= 0 && eos_token_id < t->cfg.vocab_size, QTTS_ERR_ARG, "eos_token_id");
-    hipStream_t st = (hipStream_t)stream;
-    const int V = t->cfg.vocab_size;
-    t->prefilled = false;
-    {
-        std::vector<unsigned char> m(V, 0);
-        for (int i = 0; i < n_suppress; ++i) {
-            QTTS_REQUIRE(suppress_host[i] >= 0 && suppress_host[i] < V, QTTS_ERR_ARG, "suppress token out of range");
-            m[suppress_host[i]] = 1;
-        }
-        QTTS_CHECK_HIP(hipMemcpyAsync(t->suppress.p, m.data(), V, hipMemcpyHostToDevice, st));
-        const unsigned long long seed = sp->seed;
-        QTTS_CHECK_HIP(hipMemcpyAsync(t->seed_d.p, &seed, 8, hipMemcpyHostToDevice, st));
-        QTTS_CHECK_HIP(hipStreamSynchronize(st));
-    }
-    t->gen_cap = max_new_tokens;
-    t->generated.ensure((size_t)t->B * max_new_tokens * 4);
-    auto& g = t->sg;
-    g = qtts_talker::StreamGen{};
-    g.sp = *sp; g.eos = eos_token_id; g.min_new = min_new_tokens; g.max_new = max_new_tokens;
-    g.max_frames = std::max(1, max_new_tokens - 1); g.codes = codes_dev; g.hidden = hidden_dev;
-    t->frames_run = 0;
-    t->sample_talker(*sp, eos_token_id, min_new_tokens, max_new_tokens, st);      // token 0
-    QTTS_CHECK_HIP(hipMemcpyAsync(&g.done, t->ss.done, 4, hipMemcpyDeviceToHost, st));
-    QTTS_CHECK_HIP(hipStreamSynchronize(st));
-    // the cached frame graph is reusable only when everything it baked in is unchanged (as in qtts_talker_generate)
-    qtts_talker::GraphKey key;
-    memset(&key, 0, sizeof(key));
-    key.B = t->B; key.Tt = t->Tt; key.eos = g.eos; key.min_new = g.min_new; key.max_new = g.max_new; key.max_frames = g.max_frames;
-    key.do_sample = sp->do_sample; key.top_k = sp->top_k; key.sub_do_sample = sp->subtalker_dosample;
-    key.sub_top_k = sp->subtalker_top_k; key.top_p = sp->top_p; key.temperature = sp->temperature; key.rep = sp->repetition_penalty;
-    key.sub_top_p = sp->subtalker_top_p; key.sub_temperature = sp->subtalker_temperature; key.codes = codes_dev;
-    key.hidden = hidden_dev; key.trailing = t->trailing.p; key.tts_pad = t->tts_pad.p; key.generated = t->generated.p;
-    if (!t->cfg.use_graph || !t->any_graph() || !(key == t->graph_key)) { t->destroy_graph(); t->graph_nodes = 0; }
-    t->graph_key = key;
-    g.active = true;
+    stream_begin_body(t, sp, nullptr, max_new_tokens, min_new_tokens, eos_token_id, suppress_host, n_suppress, codes_dev, hidden_dev,
+                      (hipStream_t)stream);
+    QTTS_API_END
+}
+
+int qtts_talker_stream_begin_rows(qtts_talker* t, const qtts_row_sampling* rows_host, int32_t n_rows, int32_t eos_token_id,
+                                  const int32_t* suppress_host, int32_t n_suppress, int64_t* codes_dev, float* hidden_dev, void* stream) {
+    QTTS_API_BEGIN
+    QTTS_REQUIRE(t && rows_host && codes_dev, QTTS_ERR_ARG, "null argument");
+    QTTS_REQUIRE(t->prefilled, QTTS_ERR_STATE, "stream_begin_rows: prefill() first");
+    QTTS_REQUIRE(!t->profile, QTTS_ERR_STATE, "stream_begin_rows: not available in profile mode");
+    QTTS_REQUIRE(eos_token_id >= 0 && eos_token_id < t->cfg.vocab_size, QTTS_ERR_ARG, "eos_token_id");
+    const RowTable rt = check_rows(t, rows_host, n_rows, "stream_begin_rows");
+    const qtts_sampling none{};
+    stream_begin_body(t, &none, &rt, rt.max_new, rt.poll_from, eos_token_id, suppress_host, n_suppress, codes_dev, hidden_dev, (hipStream_t)stream);
     QTTS_API_END
 }
 
@@ -1536,6 +1629,7 @@ int qtts_talker_get_stats(qtts_talker* t, qtts_talker_stats* out) {
     out->cp_mlp_per_step = t->cp_fused_slot ? t->cp_mlp_per_step : 0;
     out->cp_layer_per_step = t->cp_fused_slot ? t->cp_layer_per_step : 0;
     out->ks_split_per_step = t->ks_split_env ? t->ks_split_per_step : 0; out->attn_gq_per_step = t->attn_gq_per_step;
+    out->graph_captures = t->graph_captures; out->row_table_last = t->row_mode ? 1 : 0;
     QTTS_API_END
 }
 int qtts_talker_get_gemm_profile(qtts_talker* t, qtts_gemm_class* out, int32_t cap, int32_t* n) {

@@ -286,28 +286,44 @@ class Qwen3TTSForConditionalGeneration:
                  temperature: float = 0.9, subtalker_dosample: bool = True, subtalker_top_k: int = 50,
                  subtalker_top_p: float = 1.0, subtalker_temperature: float = 0.9, eos_token_id: Optional[int] = None,
                  repetition_penalty: float = 1.05, **kwargs):
+        """Every sampling knob, `max_new_tokens` and the `seed` keyword take one value for the call (as the reference) or a sequence with
+        one value per request; sequences are sliced per wave.  With a `seed` sequence each request keeps its own seed whichever wave
+        and row it lands in, so a request's codes do not depend on what it was batched with.  With per-request knobs but ONE `seed` s,
+        request i samples with s + i; with no seed, every request draws a fresh one: requests never share their random draws."""
         c = self.config
         embeds, mask, trailing, pad = self.assemble_prompts(input_ids, languages, speakers, instruct_ids,
                                                             non_streaming_mode, ref_ids, voice_clone_prompt)
         suppress = [i for i in range(c.vocab_size - 1024, c.vocab_size) if i != c.codec_eos_token_id]      # M:2059-2063
         codes_all, hidden_all = [], []
         mb = self.talker.max_batch
-        # one base seed per call (torch's advancing generator unless given); wave w samples with base + w so that equal rows of
-        # different waves do not repeat each other's random draws (the Philox counter is (step, row-in-wave, codebook))
-        from .talker import _fresh_seed
-        base_seed = int(kwargs["seed"]) if kwargs.get("seed") is not None else _fresh_seed()
-        for b0 in range(0, embeds.shape[0], mb):     # larger request lists run as waves of max_batch rows
+        from .talker import _fresh_seed, _is_row_seq
+        n_req = embeds.shape[0]
+        knobs = dict(max_new_tokens=max_new_tokens, do_sample=do_sample, top_k=top_k, top_p=top_p, temperature=temperature,
+                     subtalker_dosample=subtalker_dosample, subtalker_top_k=subtalker_top_k, subtalker_top_p=subtalker_top_p,
+                     subtalker_temperature=subtalker_temperature, repetition_penalty=repetition_penalty)
+        seed = kwargs.get("seed")
+        for k, v in list(knobs.items()) + [("seed", seed)]:
+            if _is_row_seq(v) and len(v) != n_req:
+                raise ValueError(f"`{k}` has {len(v)} entries for {n_req} requests")
+        # Without any per-request sequence (the scalar path): one base seed per call (torch's advancing generator unless given); wave w
+        # samples with base + w so that equal rows of different waves do not repeat each other's random draws (the scalar path's Philox
+        # counter is (step, row-in-wave, codebook)).  With one (the per-row table, whose counter has no row term) every request needs a
+        # seed of its own: a seed sequence is per request and is only sliced; ONE integer s gives request i of the call s + i,
+        # whichever wave it lands in; no seed at all leaves every row to draw a fresh one (`TalkerEngine._row_table`).
+        per_request = any(_is_row_seq(v) for v in knobs.values()) or _is_row_seq(seed)
+        if per_request:
+            seeds = list(seed) if _is_row_seq(seed) else ([int(seed) + i for i in range(n_req)] if seed is not None else [None] * n_req)
+        else:
+            base_seed = int(seed) if seed is not None else _fresh_seed()
+        for b0 in range(0, n_req, mb):     # larger request lists run as waves of max_batch rows
             sl = slice(b0, b0 + mb)
             e, m = embeds[sl], mask[sl]
             drop = int((1 - m).sum(-1).min())        # a wave may be over-padded relative to its own longest row
-            out = self.talker.generate(e[:, drop:], m[:, drop:], trailing[sl], pad, max_new_tokens=max_new_tokens,
-                                       min_new_tokens=2, do_sample=do_sample, top_k=top_k, top_p=top_p,
-                                       temperature=temperature, subtalker_dosample=subtalker_dosample,
-                                       subtalker_top_k=subtalker_top_k, subtalker_top_p=subtalker_top_p,
-                                       subtalker_temperature=subtalker_temperature,
+            wave = {k: (list(v[sl]) if _is_row_seq(v) else v) for k, v in knobs.items()}
+            out = self.talker.generate(e[:, drop:], m[:, drop:], trailing[sl], pad, min_new_tokens=2,
                                        eos_token_id=eos_token_id if eos_token_id is not None else c.codec_eos_token_id,
-                                       repetition_penalty=repetition_penalty, suppress_tokens=suppress,
-                                       seed=base_seed + b0 // mb)
+                                       suppress_tokens=suppress,
+                                       seed=seeds[sl] if per_request else base_seed + b0 // mb, **wave)
             first = out.codes[:, :, 0]
             stop = first == c.codec_eos_token_id                                                           # M:2283-2289
             for i in range(first.shape[0]):
@@ -327,7 +343,7 @@ class Qwen3TTSForConditionalGeneration:
                         repetition_penalty: float = 1.05, **kwargs):
         """Streaming OUTPUT variant of `generate` (the reference returns whole utterances, qwen3_tts_model.py:513-515): a
         generator of packets; each packet is a list with, per request, the (k_i, G) codes it gained (k_i = 0 once the
-        request hit EOS, M:2283-2289).  One wave only: len(input_ids) <= max_batch."""
+        request hit EOS, M:2283-2289).  One wave only: len(input_ids) <= max_batch.  Per-request sequences as in `generate`."""
         c = self.config
         if len(input_ids) > self.talker.max_batch:
             raise ValueError(f"generate_stream: {len(input_ids)} requests exceed max_batch {self.talker.max_batch}")
@@ -491,7 +507,11 @@ class Qwen3TTSModel:
                     subtalker_temperature=subtalker_temperature, max_new_tokens=max_new_tokens)
         merged = dict(kwargs)
         for k, dv in hard.items():
-            merged[k] = user[k] if user[k] is not None else self.generate_defaults.get(k, dv)
+            default = self.generate_defaults.get(k, dv)
+            if isinstance(user[k], (list, tuple)):      # one value per request: a None element takes what a None scalar would take
+                merged[k] = [default if v is None else v for v in user[k]]
+            else:
+                merged[k] = user[k] if user[k] is not None else default
         return merged
 
     def _unsupported(self, what: str):

@@ -83,6 +83,21 @@ def _resolve_top(top_k, top_p):
     return int(k or 0), p
 
 
+_ROW_ARGS = ("do_sample", "top_k", "top_p", "temperature", "repetition_penalty", "subtalker_dosample", "subtalker_top_k",
+             "subtalker_top_p", "subtalker_temperature", "max_new_tokens", "min_new_tokens", "seed")
+
+
+def _is_row_seq(v) -> bool:
+    """A per-request value list (list / tuple / 1-d array or tensor) as opposed to one value for the whole batch."""
+    if isinstance(v, (list, tuple)):
+        return True
+    return hasattr(v, "ndim") and hasattr(v, "__len__") and v.ndim == 1
+
+
+def _scalar(v):
+    return v.item() if hasattr(v, "item") and getattr(v, "ndim", 1) == 0 else v
+
+
 class TalkerEngine:
     """Owns one `qtts_talker` handle."""
 
@@ -192,6 +207,47 @@ class TalkerEngine:
             max_new_tokens = room
         return max_new_tokens
 
+    def _row_table(self, B: int, T: int, **kw):
+        """The per-request settings table of a call (include/qtts.h `qtts_row_sampling`), or None when every argument of `_ROW_ARGS`
+        is a scalar (the scalar path).  Any of them may be a sequence of length B; scalars are broadcast.  Every element goes through
+        the checks a scalar goes through (`_check_warpers`, `_resolve_top`, `_clamp_new_tokens`).  Seeds: a `None` (the whole argument
+        or one element) draws a fresh seed for each such row; ONE integer s gives request b the seed s + b, so that requests never share
+        their draws unless a seed list says so.  Returns (ctypes array of B entries, the largest max_new_tokens)."""
+        if not any(_is_row_seq(kw[k]) for k in _ROW_ARGS):
+            return None
+        cols = {}
+        for k in _ROW_ARGS:
+            v = kw[k]
+            if _is_row_seq(v):
+                v = [_scalar(x) for x in v]
+                if len(v) != B:
+                    raise ValueError(f"`{k}` has {len(v)} entries for a batch of {B} requests")
+            elif k == "seed" and v is not None:
+                # the table's Philox counter has no row term: ONE seed for every row would give every request the same random numbers
+                v = [int(v) + b for b in range(B)]
+            else:
+                v = [v] * B
+            cols[k] = v
+        rows = (_lib.RowSamplingC * B)()
+        for b in range(B):
+            r = {k: cols[k][b] for k in _ROW_ARGS}
+            _check_warpers(**{k: r[k] for k in ("top_k", "top_p", "temperature", "subtalker_top_k", "subtalker_top_p",
+                                                "subtalker_temperature")})
+            e = rows[b]
+            e.do_sample = 1 if r["do_sample"] else 0
+            e.top_k, e.top_p = _resolve_top(r["top_k"], r["top_p"])
+            e.temperature = float(r["temperature"]) if r["temperature"] is not None else 1.0
+            e.repetition_penalty = float(r["repetition_penalty"]) if r["repetition_penalty"] is not None else 1.0
+            e.subtalker_dosample = 1 if r["subtalker_dosample"] else 0
+            e.subtalker_top_k, e.subtalker_top_p = _resolve_top(r["subtalker_top_k"], r["subtalker_top_p"])
+            e.subtalker_temperature = float(r["subtalker_temperature"]) if r["subtalker_temperature"] is not None else 1.0
+            if r["max_new_tokens"] is None or int(r["max_new_tokens"]) < 1:
+                raise ValueError(f"`max_new_tokens` of request {b} must be a positive integer, but is {r['max_new_tokens']}")
+            e.max_new_tokens = self._clamp_new_tokens(T, int(r["max_new_tokens"]))
+            e.min_new_tokens = int(r["min_new_tokens"]) if r["min_new_tokens"] is not None else 0
+            e.seed = int(r["seed"]) & 0xFFFFFFFFFFFFFFFF if r["seed"] is not None else _fresh_seed()
+        return rows, max(int(rows[b].max_new_tokens) for b in range(B))
+
     # ------------------------------------------------------------------ generate (seam S2)
     @_lib.locked
     def text_embed(self, ids: torch.Tensor) -> torch.Tensor:
@@ -263,7 +319,14 @@ class TalkerEngine:
                  logit_steps: Optional[List[int]] = None, **unused) -> TalkerGenerateOutput:
         """`teacher_codes` (B, F, G) switches on the diagnostic teacher-forced mode (include/qtts.h `qtts_talker_set_teacher`):
         greedy, exactly F frames; the engine's own choices come back in `.own`, the raw cb-0 logits of the token steps listed in
-        `logit_steps` in `.logits_trace`."""
+        `logit_steps` in `.logits_trace`.
+
+        Per-request settings: each of `do_sample`, `top_k`, `top_p`, `temperature`, `repetition_penalty`, the four `subtalker_*`
+        knobs, `max_new_tokens`, `min_new_tokens` and `seed` is one value for the batch (as in the reference) or a sequence of B
+        values, one per request.  With any sequence the call runs on the engine's per-row table (`qtts_talker_generate_rows`): a
+        request's draws then depend on its own seed only -- not on its row or on the other requests -- and changing the values between
+        calls does not re-capture the frame graph.  Request b's frames are `codes[b]` up to its first eos in codebook 0; a request
+        that reached its own `max_new_tokens` m receives eos from `tokens[b, m - 1]` on (a scalar run keeps the sampled token there)."""
         c = self.config
         if inputs_embeds.dim() != 3 or inputs_embeds.shape[-1] != c.hidden_size:
             raise ValueError(f"inputs_embeds must be (B, T, {c.hidden_size})")
@@ -285,21 +348,31 @@ class TalkerEngine:
         expect = (torch.arange(T)[None, :] >= n_pad[:, None]).long()
         if not torch.equal(mask, expect) or int(n_pad.max()) >= T:
             raise ValueError("attention_mask must be left-padded: [0]*n_pad + [1]*(T-n_pad) per row")
-        max_new_tokens = self._clamp_new_tokens(T, int(max_new_tokens))
+        table = self._row_table(B, T, do_sample=do_sample, top_k=top_k, top_p=top_p, temperature=temperature,
+                                repetition_penalty=repetition_penalty, subtalker_dosample=subtalker_dosample,
+                                subtalker_top_k=subtalker_top_k, subtalker_top_p=subtalker_top_p,
+                                subtalker_temperature=subtalker_temperature, max_new_tokens=max_new_tokens,
+                                min_new_tokens=min_new_tokens, seed=seed)
         eos = c.codec_eos_token_id if eos_token_id is None else int(eos_token_id)
         if suppress_tokens is None:
             suppress_tokens = []
-        _check_warpers(top_k=top_k, top_p=top_p, temperature=temperature, subtalker_top_k=subtalker_top_k,
-                       subtalker_top_p=subtalker_top_p, subtalker_temperature=subtalker_temperature)
-        sp = _lib.SamplingC()
-        sp.do_sample = 1 if do_sample else 0
-        sp.top_k, sp.top_p = _resolve_top(top_k, top_p)
-        sp.temperature = float(temperature) if temperature is not None else 1.0
-        sp.repetition_penalty = float(repetition_penalty) if repetition_penalty is not None else 1.0
-        sp.subtalker_dosample = 1 if subtalker_dosample else 0
-        sp.subtalker_top_k, sp.subtalker_top_p = _resolve_top(subtalker_top_k, subtalker_top_p)
-        sp.subtalker_temperature = float(subtalker_temperature) if subtalker_temperature is not None else 1.0
-        sp.seed = int(seed) & 0xFFFFFFFFFFFFFFFF if seed is not None else _fresh_seed()
+        if table is not None:
+            if teacher_codes is not None:
+                raise ValueError("teacher_codes takes scalar settings, not per-request sequences")
+            rows, max_new_tokens = table                  # buffers are sized by the largest limit
+        else:
+            max_new_tokens = self._clamp_new_tokens(T, int(max_new_tokens))
+            _check_warpers(top_k=top_k, top_p=top_p, temperature=temperature, subtalker_top_k=subtalker_top_k,
+                           subtalker_top_p=subtalker_top_p, subtalker_temperature=subtalker_temperature)
+            sp = _lib.SamplingC()
+            sp.do_sample = 1 if do_sample else 0
+            sp.top_k, sp.top_p = _resolve_top(top_k, top_p)
+            sp.temperature = float(temperature) if temperature is not None else 1.0
+            sp.repetition_penalty = float(repetition_penalty) if repetition_penalty is not None else 1.0
+            sp.subtalker_dosample = 1 if subtalker_dosample else 0
+            sp.subtalker_top_k, sp.subtalker_top_p = _resolve_top(subtalker_top_k, subtalker_top_p)
+            sp.subtalker_temperature = float(subtalker_temperature) if subtalker_temperature is not None else 1.0
+            sp.seed = int(seed) & 0xFFFFFFFFFFFFFFFF if seed is not None else _fresh_seed()
 
         dev = self.device
         emb = inputs_embeds.to(dev, torch.float32).contiguous()
@@ -344,11 +417,14 @@ class TalkerEngine:
                 _lib.check(self._lib.qtts_talker_set_teacher(self._h, C.c_void_p(tc.data_ptr()), F_t, C.c_void_p(own.data_ptr()),
                                                              C.c_void_p(slots.data_ptr()) if trace is not None else None,
                                                              C.c_void_p(trace.data_ptr()) if trace is not None else None))
+            out_c = (C.c_void_p(codes.data_ptr()), C.c_void_p(hidden.data_ptr()) if hidden is not None else None,
+                     C.c_void_p(tokens.data_ptr()), C.byref(n_frames), self._s())
             try:
-                _lib.check(self._lib.qtts_talker_generate(
-                    self._h, C.byref(sp), int(max_new_tokens), int(min_new_tokens), eos, sup_c, len(suppress_tokens),
-                    C.c_void_p(codes.data_ptr()), C.c_void_p(hidden.data_ptr()) if hidden is not None else None,
-                    C.c_void_p(tokens.data_ptr()), C.byref(n_frames), self._s()))
+                if table is not None:
+                    _lib.check(self._lib.qtts_talker_generate_rows(self._h, rows, B, eos, sup_c, len(suppress_tokens), *out_c))
+                else:
+                    _lib.check(self._lib.qtts_talker_generate(self._h, C.byref(sp), int(max_new_tokens), int(min_new_tokens), eos,
+                                                              sup_c, len(suppress_tokens), *out_c))
             finally:
                 if teacher_codes is not None:
                     _lib.check(self._lib.qtts_talker_set_teacher(self._h, None, 0, None, None, None))
@@ -366,8 +442,8 @@ class TalkerEngine:
                         repetition_penalty: float = 1.05, suppress_tokens: Optional[List[int]] = None,
                         seed: Optional[int] = None, **unused):
         """Streaming OUTPUT (include/qtts.h `qtts_talker_stream_*`): a generator that yields `codes[:, f0:f1]` (B, k, G)
-        int64 device tensors, k <= packet_frames, as the frames are produced; same arguments and the same frames as
-        `generate`.  Closing the generator early abandons the request.  Holds the engine lock while active."""
+        int64 device tensors, k <= packet_frames, as the frames are produced; same arguments (per-request sequences included) and the
+        same frames as `generate`.  Closing the generator early abandons the request.  Holds the engine lock while active."""
         c = self.config
         if inputs_embeds.dim() != 3 or inputs_embeds.shape[-1] != c.hidden_size:
             raise ValueError(f"inputs_embeds must be (B, T, {c.hidden_size})")
@@ -384,20 +460,28 @@ class TalkerEngine:
         expect = (torch.arange(T)[None, :] >= n_pad[:, None]).long()
         if not torch.equal(mask, expect) or int(n_pad.max()) >= T:
             raise ValueError("attention_mask must be left-padded: [0]*n_pad + [1]*(T-n_pad) per row")
-        max_new_tokens = self._clamp_new_tokens(T, int(max_new_tokens))
+        table = self._row_table(B, T, do_sample=do_sample, top_k=top_k, top_p=top_p, temperature=temperature,
+                                repetition_penalty=repetition_penalty, subtalker_dosample=subtalker_dosample,
+                                subtalker_top_k=subtalker_top_k, subtalker_top_p=subtalker_top_p,
+                                subtalker_temperature=subtalker_temperature, max_new_tokens=max_new_tokens,
+                                min_new_tokens=min_new_tokens, seed=seed)
         eos = c.codec_eos_token_id if eos_token_id is None else int(eos_token_id)
         suppress_tokens = list(suppress_tokens or [])
-        _check_warpers(top_k=top_k, top_p=top_p, temperature=temperature, subtalker_top_k=subtalker_top_k,
-                       subtalker_top_p=subtalker_top_p, subtalker_temperature=subtalker_temperature)
-        sp = _lib.SamplingC()
-        sp.do_sample = 1 if do_sample else 0
-        sp.top_k, sp.top_p = _resolve_top(top_k, top_p)
-        sp.temperature = float(temperature) if temperature is not None else 1.0
-        sp.repetition_penalty = float(repetition_penalty) if repetition_penalty is not None else 1.0
-        sp.subtalker_dosample = 1 if subtalker_dosample else 0
-        sp.subtalker_top_k, sp.subtalker_top_p = _resolve_top(subtalker_top_k, subtalker_top_p)
-        sp.subtalker_temperature = float(subtalker_temperature) if subtalker_temperature is not None else 1.0
-        sp.seed = int(seed) & 0xFFFFFFFFFFFFFFFF if seed is not None else _fresh_seed()
+        if table is not None:
+            rows, max_new_tokens = table
+        else:
+            max_new_tokens = self._clamp_new_tokens(T, int(max_new_tokens))
+            _check_warpers(top_k=top_k, top_p=top_p, temperature=temperature, subtalker_top_k=subtalker_top_k,
+                           subtalker_top_p=subtalker_top_p, subtalker_temperature=subtalker_temperature)
+            sp = _lib.SamplingC()
+            sp.do_sample = 1 if do_sample else 0
+            sp.top_k, sp.top_p = _resolve_top(top_k, top_p)
+            sp.temperature = float(temperature) if temperature is not None else 1.0
+            sp.repetition_penalty = float(repetition_penalty) if repetition_penalty is not None else 1.0
+            sp.subtalker_dosample = 1 if subtalker_dosample else 0
+            sp.subtalker_top_k, sp.subtalker_top_p = _resolve_top(subtalker_top_k, subtalker_top_p)
+            sp.subtalker_temperature = float(subtalker_temperature) if subtalker_temperature is not None else 1.0
+            sp.seed = int(seed) & 0xFFFFFFFFFFFFFFFF if seed is not None else _fresh_seed()
         dev = self.device
         emb = inputs_embeds.to(dev, torch.float32).contiguous()
         trail = trailing_text_hidden.to(dev, torch.float32).contiguous()
@@ -416,9 +500,13 @@ class TalkerEngine:
                 _lib.check(self._lib.qtts_talker_prefill(self._h, C.c_void_p(emb.data_ptr()), B, T, npad_c,
                                                          C.c_void_p(trail.data_ptr()), trail.shape[1],
                                                          C.c_void_p(pad.data_ptr()), self._s()))
-                _lib.check(self._lib.qtts_talker_stream_begin(self._h, C.byref(sp), int(max_new_tokens), int(min_new_tokens), eos,
-                                                              sup_c, len(suppress_tokens), C.c_void_p(codes.data_ptr()), None,
-                                                              self._s()))
+                if table is not None:
+                    _lib.check(self._lib.qtts_talker_stream_begin_rows(self._h, rows, B, eos, sup_c, len(suppress_tokens),
+                                                                       C.c_void_p(codes.data_ptr()), None, self._s()))
+                else:
+                    _lib.check(self._lib.qtts_talker_stream_begin(self._h, C.byref(sp), int(max_new_tokens), int(min_new_tokens), eos,
+                                                                  sup_c, len(suppress_tokens), C.c_void_p(codes.data_ptr()), None,
+                                                                  self._s()))
             seen = 0
             try:
                 while not fin.value:
