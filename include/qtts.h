@@ -49,8 +49,10 @@ const char* qtts_last_error(void);
  * 11: + qtts_talker_debug_cp_logits, qtts_talker_stats.cp_layer_per_step in the reserved word;
  * 12: + qtts_talker_stats.ks_split_per_step (appended); 13: qtts_talker_stats.attn_gq_per_step in the reserved word, the talker
  * engine takes head_dim 64 | 128 and GQA groups of 1..8; 14: + qtts_row_sampling, qtts_talker_generate_rows,
- * qtts_talker_stream_begin_rows, qtts_talker_stats.graph_captures / row_table_last (appended)). */
-#define QTTS_ABI_VERSION 14
+ * qtts_talker_stream_begin_rows, qtts_talker_stats.graph_captures / row_table_last (appended); 15: + qtts_talker_stream_begin_admitting,
+ * qtts_talker_stream_admit, qtts_talker_stream_rows, qtts_talker_stats.admit_calls / admitted_rows (two words IN FRONT of row_table_last:
+ * the struct's tail moved by 8 bytes)). */
+#define QTTS_ABI_VERSION 15
 int qtts_abi_version(void);
 
 /* A/B switches of the library (measuring tools and tests; a deployment sets none).  Every switch has a name of the form
@@ -432,6 +434,40 @@ int qtts_talker_stream_step(qtts_talker* t, int32_t max_frames_now, int32_t* fra
                             void* stream);
 int qtts_talker_stream_end(qtts_talker* t, int64_t* tokens_dev, int32_t* n_frames_host, void* stream);
 
+/* Admission of queued requests into finished rows of a running stream (ABI v15; no reference counterpart: the reference hands one static
+ * batch to HF generate, modeling_qwen3_tts.py:2272-2278 -- each request's result is still what the reference produces for that request).
+ * A stream has ONE position, kv_len: the slot the next frame step writes in every row.  A request with a prompt of T_new rows is admitted
+ * into a finished row by writing its prompt's K/V into slots [kv_len - T_new, kv_len) of that row; from then on the row looks like a
+ * request that was left-padded that far, and everything that counts per request -- token history, min_new_tokens, the row's limit, the
+ * trailing-text index, the frame index of its outputs, the Philox step -- counts from the row's own origin.  A request's draws are a
+ * function of (its seed, its own step, codebook) whenever it was admitted.
+ *   stream_begin_admitting  qtts_talker_stream_begin_rows plus max_row_tokens: codes_dev (B, max_row_tokens - 1, G), hidden_dev
+ *                 (B, max_row_tokens - 1, H; optional) and the token history hold ONE occupant per row at a time; frame f of a row's
+ *                 occupant is codes_dev[row][f].  The stream's stop condition is "no row unfinished"; how far it can run is bounded by
+ *                 max_seq, which is checked per admission.  Refused like stream_begin_rows, and (QTTS_ERR_LIMIT, naming the row) when a
+ *                 row's max_new_tokens exceeds max_row_tokens.
+ *   stream_admit  between two stream_step calls, on the same stream: rows_host[i] is the finished row request i takes; embeds_dev
+ *                 (n_new, T, H) LEFT-padded inside T with n_pad_host[i] pads (T: the longest prompt of the group); trailing_dev
+ *                 (n_new, Tt, H), padded by the engine with tts_pad to the stream's trailing capacity; settings_host[i] the request's
+ *                 knobs.  Samples token 0 of the admitted rows only; the stream's counters do not move, the other rows' state is not
+ *                 touched, and the captured frame graphs are replayed unchanged (graph_captures does not advance; the one exception is an
+ *                 occupant outside the fast samplers' class entering a stream that ran inside it).  Refused, the message naming the row:
+ *                 no admitting stream open (QTTS_ERR_STATE); a row index >= B, listed twice, or still unfinished (QTTS_ERR_ARG); a prompt
+ *                 longer than kv_len, kv_len + max_new_tokens beyond max_seq, max_new_tokens > max_row_tokens, Tt beyond the stream's
+ *                 trailing capacity (QTTS_ERR_LIMIT); the settings checks of qtts_talker_generate_rows (QTTS_ERR_ARG).  A refused call
+ *                 changes nothing.  The caller copies a finished row's frames out BEFORE admitting into it.
+ *   stream_rows   per row: whether its occupant is still running and how many of its frames are final (they end before its first eos in
+ *                 codebook 0); and the shared position.  Synchronises the stream the stream was begun on.
+ * stream_step / stream_end are the same calls; for an admitting stream frames_total / n_frames count the STREAM's frame steps and
+ * tokens_dev is (B, max_row_tokens), each row's current occupant. */
+int qtts_talker_stream_begin_admitting(qtts_talker* t, const qtts_row_sampling* rows_host, int32_t n_rows, int32_t max_row_tokens,
+                                       int32_t eos_token_id, const int32_t* suppress_host, int32_t n_suppress, int64_t* codes_dev,
+                                       float* hidden_dev, void* stream);
+int qtts_talker_stream_admit(qtts_talker* t, int32_t n_new, const int32_t* rows_host, const float* embeds_dev, int32_t T,
+                             const int32_t* n_pad_host, const float* trailing_dev, int32_t Tt, const qtts_row_sampling* settings_host,
+                             void* stream);
+int qtts_talker_stream_rows(qtts_talker* t, int32_t* unfinished_host, int32_t* frames_host, int32_t* kv_len_host);
+
 /* Test/diagnostic hooks (device -> caller device buffers, after prefill / a generate call). */
 int qtts_talker_debug_logits(qtts_talker* t, float* logits_dev /* (B, vocab) */, void* stream);
 /* The code predictor's RAW logits of the last frame step that ran, every pass: what `code_predictor.generate`'s lm_head[j] returned
@@ -462,6 +498,8 @@ typedef struct {
                                      * bf16 engines at batch 17..32: the o- / down-projections; ABI v12)                                       */
     int32_t attn_gq_per_step;       /* decode-attention launches of that frame step that ran the general kernel family (attn_gq.h: any head shape beyond
                                      * head_dim 128 with a group <= 2, or every launch under QTTS_ATTN_GQ=1; ABI v13: the former reserved word) */
+    int32_t admit_calls;            /* qtts_talker_stream_admit calls that succeeded on the last stream (ABI v15) ...        */
+    int32_t admitted_rows;          /* ... and the rows they admitted                                                        */
     int32_t row_table_last;         /* 1: the last generation ran with a per-row settings table (qtts_talker_generate_rows; ABI v14) */
     int64_t graph_captures;         /* frame-graph captures over the engine's life: a call that replays a cached graph adds none (ABI v14) */
 } qtts_talker_stats;

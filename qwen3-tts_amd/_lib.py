@@ -81,6 +81,7 @@ class TalkerStatsC(C.Structure):
                 ("cp_fused_launches_last", C.c_int64), ("cp_fused_giveups", C.c_int32), ("cp_fused_capacity", C.c_int32),
                 ("cp_fused_active", C.c_int32), ("cp_mlp_per_step", C.c_int32), ("cp_layer_per_step", C.c_int32),
                 ("ks_split_per_step", C.c_int32), ("attn_gq_per_step", C.c_int32),
+                ("admit_calls", C.c_int32), ("admitted_rows", C.c_int32),
                 ("row_table_last", C.c_int32), ("graph_captures", C.c_int64)]
 
 
@@ -93,7 +94,7 @@ class GemmClassC(C.Structure):
                 ("min_us", C.c_double), ("max_us", C.c_double), ("bytes_per_launch", C.c_double)]
 
 
-ABI_VERSION = 14          # include/qtts.h; bumped on any signature change
+ABI_VERSION = 15          # include/qtts.h; bumped on any signature change
 
 # every symbol include/qtts.h declares (checked by tests/test_host_logic.py::test_abi_exports_every_declared_symbol without a GPU)
 SYMBOLS = ["qtts_last_error", "qtts_abi_version", "qtts_set_option", "qtts_get_option", "qtts_codec_create", "qtts_codec_destroy", "qtts_codec_bind",
@@ -107,6 +108,7 @@ SYMBOLS = ["qtts_last_error", "qtts_abi_version", "qtts_set_option", "qtts_get_o
            "qtts_talker_text_projection", "qtts_talker_text_embed", "qtts_talker_assemble_rows", "qtts_talker_prefill",
            "qtts_talker_generate", "qtts_talker_stream_begin", "qtts_talker_stream_step", "qtts_talker_stream_end",
            "qtts_talker_generate_rows", "qtts_talker_stream_begin_rows",
+           "qtts_talker_stream_begin_admitting", "qtts_talker_stream_admit", "qtts_talker_stream_rows",
            "qtts_talker_debug_logits", "qtts_talker_debug_cp_logits", "qtts_talker_get_stats", "qtts_talker_get_gemm_profile", "qtts_talker_set_teacher",
            "qtts_talker_set_profile"]
 
@@ -193,6 +195,10 @@ def load_library():
     lib.qtts_talker_generate_rows.argtypes = [vp, C.POINTER(RowSamplingC), i32, i32, C.POINTER(C.c_int32), i32, vp, vp, vp,
                                               C.POINTER(C.c_int32), vp]
     lib.qtts_talker_stream_begin_rows.argtypes = [vp, C.POINTER(RowSamplingC), i32, i32, C.POINTER(C.c_int32), i32, vp, vp, vp]
+    lib.qtts_talker_stream_begin_admitting.argtypes = [vp, C.POINTER(RowSamplingC), i32, i32, i32, C.POINTER(C.c_int32), i32, vp, vp, vp]
+    lib.qtts_talker_stream_admit.argtypes = [vp, i32, C.POINTER(C.c_int32), f32p, i32, C.POINTER(C.c_int32), f32p, i32,
+                                             C.POINTER(RowSamplingC), vp]
+    lib.qtts_talker_stream_rows.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     lib.qtts_talker_stream_step.argtypes = [vp, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp]
     lib.qtts_talker_stream_end.argtypes = [vp, vp, C.POINTER(C.c_int32), vp]
     lib.qtts_talker_debug_logits.argtypes = [vp, f32p, vp]

@@ -282,6 +282,8 @@ __global__ __launch_bounds__(256) void qknorm_rope_store_kernel(QkNormRopeParams
     const int t = (int)(blockIdx.x % p.T);
     const int b = (int)(blockIdx.x / p.T);
     const int npad = p.n_pad[b];
+    const int cb = p.row_map ? p.row_map[b] : b;       // the cache row and slot this (b, t) lands in (an admitted group: other row, offset slots)
+    const int cs = p.slot_base + t;
     if (t < npad) return;  // pad rows: K/V slots stay unused (masked by s < n_pad everywhere)
     const int hd = p.hd, half = hd / 2;
     KVT* kc = reinterpret_cast<KVT*>(p.kv.k);
@@ -308,11 +310,11 @@ __global__ __launch_bounds__(256) void qknorm_rope_store_kernel(QkNormRopeParams
             float* v = row + hh * hd;
             if (hh >= p.nh + p.nkv) {  // value head: straight copy (or, for a transposed-V cache, dim-major inside the page)
                 const int kvh = hh - p.nh - p.nkv;
-                const size_t o = kv_offset(p.kv, p.layer, b, t, kvh);
+                const size_t o = kv_offset(p.kv, p.layer, cb, cs, kvh);
                 if (p.kv.vt) {
-                    const size_t pg = o - (size_t)(t & 15) * hd;              // start of this (page, kv head) block
-                    if (lane < hd) vc[pg + (size_t)lane * 16 + (t & 15)] = kv_cast<KVT>(xa[i]);
-                    if (lane + 64 < hd) vc[pg + (size_t)(lane + 64) * 16 + (t & 15)] = kv_cast<KVT>(xb[i]);
+                    const size_t pg = o - (size_t)(cs & 15) * hd;             // start of this (page, kv head) block
+                    if (lane < hd) vc[pg + (size_t)lane * 16 + (cs & 15)] = kv_cast<KVT>(xa[i]);
+                    if (lane + 64 < hd) vc[pg + (size_t)(lane + 64) * 16 + (cs & 15)] = kv_cast<KVT>(xb[i]);
                 } else {
                     if (lane < hd) vc[o + lane] = kv_cast<KVT>(xa[i]);
                     if (lane + 64 < hd) vc[o + lane + 64] = kv_cast<KVT>(xb[i]);
@@ -339,7 +341,7 @@ __global__ __launch_bounds__(256) void qknorm_rope_store_kernel(QkNormRopeParams
             if (lane < hd) v[lane] = o0;
             if (lane + 64 < hd) v[lane + 64] = o1;
             if (is_k) {
-                const size_t o = kv_offset(p.kv, p.layer, b, t, hh - p.nh);
+                const size_t o = kv_offset(p.kv, p.layer, cb, cs, hh - p.nh);
                 if (lane < hd) kc[o + lane] = kv_cast<KVT>(o0);
                 if (lane + 64 < hd) kc[o + lane + 64] = kv_cast<KVT>(o1);
             }
@@ -350,6 +352,7 @@ __global__ __launch_bounds__(256) void qknorm_rope_store_kernel(QkNormRopeParams
 
 void launch_qknorm_rope_store(const QkNormRopeParams& p, hipStream_t st) {
     QTTS_REQUIRE(p.hd == 64 || p.hd == 128, QTTS_ERR_ARG, "qknorm_rope_store: head_dim 64|128");
+    QTTS_REQUIRE(p.slot_base >= 0 && p.slot_base + p.T <= p.kv.pages_per_seq * 16, QTTS_ERR_LIMIT, "qknorm_rope_store: slots beyond the cache row");
     const int grid = p.B * p.T;                        // a workgroup per (b, t) row
     if (p.kv.bf16) hipLaunchKernelGGL(qknorm_rope_store_kernel<bf16_t>, dim3(grid), dim3(256), 0, st, p);
     else hipLaunchKernelGGL(qknorm_rope_store_kernel<float>, dim3(grid), dim3(256), 0, st, p);

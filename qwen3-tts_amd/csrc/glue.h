@@ -51,6 +51,9 @@ struct EmbedSumParams {
     const float* past_hidden;
     float* x_out; unsigned short* x_out16;   // fp32 hidden state (+ optional bf16 copy)
     int64_t* codes_out; float* hidden_out; int max_frames;
+    // per-row settings table: word `origin` of entry b (kernels.h: SampleRow), entries row_origin_stride ints apart, or null.  The row's
+    // frame index -- trailing text, codes_out, hidden_out -- is gen_step - origin.
+    const int* row_origin = nullptr; int row_origin_stride = 0;
     StepState st;
 };
 void launch_embed_sum(const EmbedSumParams& p, hipStream_t st);

@@ -206,6 +206,8 @@ struct QkNormRopeParams {
     const float* inv_freq;       // [hd/2]
     const int* n_pad;            // [B]
     KvCache kv; int layer;
+    // prefill at an offset (qtts_talker_stream_admit): local row b stores its K/V into cache row row_map[b] (null: b) at slots slot_base + t
+    const int* row_map = nullptr; int slot_base = 0;
 };
 void launch_qknorm_rope_store(const QkNormRopeParams& p, hipStream_t st);
 
@@ -343,7 +345,9 @@ void cp_layer_set_launch_events(hipEvent_t start, hipEvent_t stop);
 struct SampleRow {
     int do_sample; int top_k; float top_p; float temperature;                   // words 0..3: the talker's sampler
     int sub_do_sample; int sub_top_k; float sub_top_p; float sub_temperature;   // words 4..7: the code predictor's samplers
-    float repetition_penalty; int max_new_tokens; int min_new_tokens; int pad0; // words 8..11: talker only
+    float repetition_penalty; int max_new_tokens; int min_new_tokens;           // words 8..10: talker only
+    int origin;     // word 11: the stream's step count (gen_step) when this occupant was admitted into the row (qtts_talker_stream_admit), 0 for a
+                    // row that began with the stream.  Everything that counts per request counts from it: history, floor, limit, frame index, Philox step.
     unsigned long long seed;
     int pad1, pad2;
 };

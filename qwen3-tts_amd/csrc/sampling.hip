@@ -42,6 +42,7 @@ constexpr int CAND_MAX = 1024;          // top-k candidates (scores >= the k-th 
 // across the workgroup).  `limit`: the row's own max_new_tokens (table mode; otherwise no row limit: sample_finish_kernel stops the call).
 struct RowKnobs {
     int do_sample, top_k, min_new, limit;
+    int origin;                        // table mode: the stream step at which the row's occupant was admitted (0: with the stream); its counts start there
     float top_p, temperature, rep;
     unsigned long long seed;
     uint32_t ctr_row;                  // second word of the Philox counter: the row index, or 0 in table mode
@@ -67,6 +68,7 @@ __device__ __forceinline__ RowKnobs row_knobs(const SampleParams& p, int b) {
     k.rep = tab ? (sub ? 1.0f : __uint_as_float(w2.x)) : p.repetition_penalty;
     k.min_new = tab ? (int)w2.z : p.min_new_tokens;
     k.limit = tab ? (int)w2.y : 0x7fffffff;
+    k.origin = tab ? (int)w2.w : 0;
     k.seed = (tab || p.seed_dev) ? seed_mem : p.seed;
     k.ctr_row = tab ? 0u : (uint32_t)b;
     return k;
@@ -79,7 +81,8 @@ __device__ __forceinline__ int finish_row(const SampleParams& p, int b, int n_ge
         const int uf = p.unfinished[b];
         if (!uf || n_gen >= limit - 1) token = p.eos;
         p.unfinished[b] = uf && (token != p.eos);
-        if (p.generated_out) p.generated_out[(size_t)b * p.gen_stride + n_gen] = token;
+        // (a finished row of an admitting stream idles until its next occupant: its count runs past the history's capacity)
+        if (p.generated_out && n_gen < p.gen_stride) p.generated_out[(size_t)b * p.gen_stride + n_gen] = token;
     }
     p.tok_out[(size_t)b * p.tok_stride] = token;
     return token;
@@ -148,12 +151,14 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleParams p) {
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int V = p.V;
     const float* lg = p.logits + (size_t)b * p.ld;
-    const int n_gen = p.n_generated_dev ? *p.n_generated_dev : 0;
+    const int n_gen_s = p.n_generated_dev ? *p.n_generated_dev : 0;
     const RowKnobs kn = row_knobs(p, b);
+    const int n_gen = p.n_generated_dev ? n_gen_s - kn.origin : 0;      // the ROW's token count: its history, floor, limit and write index
+    const int n_hist = min(n_gen, p.gen_stride);
     for (int v = tid; v < V; v += 256) sc[v] = lg[v];
     __syncthreads();
     if (p.generated && kn.rep != 1.0f) {
-        for (int i = tid; i < n_gen; i += 256) {
+        for (int i = tid; i < n_hist; i += 256) {
             const int tok = p.generated[(size_t)b * p.gen_stride + i];
             const float s = lg[tok];
             sc[tok] = s < 0.f ? s * kn.rep : s / kn.rep;  // same value for duplicates
@@ -193,7 +198,7 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleParams p) {
             for (int v = tid; v < V; v += 256) sc[v] = sc[v] / kn.temperature;
             __syncthreads();
         }
-        const uint32_t step = p.step_dev ? (uint32_t)*p.step_dev : 0u;
+        const uint32_t step = p.step_dev ? (uint32_t)(*p.step_dev - kn.origin) : 0u;       // the row's own step
         uint32_t rnd[4];
         philox4x32_10(step, kn.ctr_row, p.stream_id, 0u, (uint32_t)kn.seed, (uint32_t)(kn.seed >> 32), rnd);
         const float u = (float)(rnd[0] >> 8) * (1.0f / 16777216.0f);
@@ -502,9 +507,12 @@ __global__ __launch_bounds__(256) void sample_kernel_v2(SampleParams p) {
     const float* lg = p.logits + (size_t)b * p.ld;
     // ---- 0. independent loads, all in flight together
     const int done = p.done_in ? *p.done_in : 0;
-    const int n_gen = p.n_generated_dev ? *p.n_generated_dev : 0;
-    const uint32_t step = p.step_dev ? (uint32_t)*p.step_dev : 0u;
+    const int n_gen_s = p.n_generated_dev ? *p.n_generated_dev : 0;
+    const int step_s = p.step_dev ? *p.step_dev : 0;
     const RowKnobs kn = row_knobs(p, b);       // (table mode: the row's 64-byte entry, requested here with everything else)
+    const int n_gen = p.n_generated_dev ? n_gen_s - kn.origin : 0;      // the ROW's token count and step (sample_kernel)
+    const int n_hist = min(n_gen, p.gen_stride);
+    const uint32_t step = p.step_dev ? (uint32_t)(step_s - kn.origin) : 0u;
     // the first 256 entries of this row's token history (repetition penalty; the talker's call only) are requested here, before the
     // count is known: behind the flag-clearing barrier below the load was a memory round trip of its own (2-6 us by box)
     const int* gsrc = p.generated ? p.generated + (size_t)b * p.gen_stride + (tid < p.gen_stride ? tid : 0) : reinterpret_cast<const int*>(lg);
@@ -524,8 +532,8 @@ __global__ __launch_bounds__(256) void sample_kernel_v2(SampleParams p) {
 #pragma unroll
         for (int it = 0; it < EPT; ++it) sc[it * 256 + tid] = 0.f;
         __syncthreads();
-        if (tid < n_gen && gtok0 >= 0 && gtok0 < V) sc[gtok0] = 1.f;          // entries 0..255: prefetched at entry
-        for (int i = tid + 256; i < n_gen; i += 256) {
+        if (tid < n_hist && gtok0 >= 0 && gtok0 < V) sc[gtok0] = 1.f;          // entries 0..255: prefetched at entry
+        for (int i = tid + 256; i < n_hist; i += 256) {
             const int tok = p.generated[(size_t)b * p.gen_stride + i];
             if (tok >= 0 && tok < V) sc[tok] = 1.f;
         }
@@ -840,7 +848,9 @@ __global__ __launch_bounds__(256) void embed_sum_kernel(EmbedSumParams p) {
 #pragma unroll
     for (int i = 0; i < GMAX; ++i) tk[i] = p.sub[(size_t)b * p.sub_stride + (i < ncp ? i : 0)];
     const int done = *p.st.done;
-    const int f = *p.st.gen_step;          // frame index == generation_step
+    const int f_s = *p.st.gen_step;        // frame index == generation_step ...
+    const int org = p.row_origin ? p.row_origin[(size_t)b * p.row_origin_stride] : 0;
+    const int f = f_s - org;               // ... of the ROW: an occupant admitted at stream step `org` starts at frame 0
     const int tok0 = p.cur_tok[b];
     if (done) return;
     for (int c = threadIdx.x * 4; c < p.H; c += 1024) {
@@ -865,7 +875,7 @@ __global__ __launch_bounds__(256) void embed_sum_kernel(EmbedSumParams p) {
             ushort4 h; h.x = f32_to_bf16(a.x); h.y = f32_to_bf16(a.y); h.z = f32_to_bf16(a.z); h.w = f32_to_bf16(a.w);
             *reinterpret_cast<ushort4*>(p.x_out16 + (size_t)b * p.H + c) = h;
         }
-        if (p.hidden_out) {
+        if (p.hidden_out && f < p.max_frames) {        // (an idle finished row of an admitting stream runs past its buffers)
             const float4 h = *reinterpret_cast<const float4*>(p.past_hidden + (size_t)b * p.H + c);
             *reinterpret_cast<float4*>(p.hidden_out + ((size_t)b * p.max_frames + f) * p.H + c) = h;
         }

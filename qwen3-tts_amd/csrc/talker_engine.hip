@@ -70,6 +70,9 @@ struct qtts_talker {
     DevBuf cur_tok, sub, generated, ss_rows, ints, n_pad_d, suppress, trailing, tts_pad;
     // prefill scratch
     DevBuf pf_x, pf_n, pf_qkv, pf_att, pf_act, tp_tmp;
+    // admission into a running stream (qtts_talker_stream_admit): the group's row map and local pads, and the staging rows of its
+    // last-position hidden, past_hidden and logits (the running rows' buffers are not touched)
+    DevBuf adm_rows_d, adm_npad_d, adm_x, adm_ph, adm_lg;
     StepState ss;
     int B = 0, T0 = 0, Tt = 0, gen_cap = 0;
     // graph
@@ -111,7 +114,16 @@ struct qtts_talker {
         qtts_sampling sp{};
         int eos = 0, min_new = 0, max_new = 0, max_frames = 0, launched = 0, done = 0;
         int64_t* codes = nullptr; float* hidden = nullptr;
+        int total = 0;                 // frame steps the stream can run at most
+        // an admitting stream (qtts_talker_stream_begin_admitting): rows are re-occupied while the others keep running.  `max_row`: the
+        // capacity of a row's outputs and token history (ONE occupant at a time); `tab`: the host's copy of the device table, with every
+        // occupant's origin
+        bool admitting = false;
+        int max_row = 0;
+        std::vector<SampleRow> tab;
+        hipStream_t st = nullptr;
     } sg;
+    int64_t admit_calls = 0, admitted_rows = 0;      // of the last stream
     int graph_nodes = 0;
     // teacher forcing (diagnostic mode, eager only): qtts_talker_set_teacher
     struct Teacher { const int64_t* codes = nullptr; int F = 0; int* own = nullptr; const int* slots = nullptr; float* trace = nullptr; } tf;
@@ -534,6 +546,9 @@ struct qtts_talker {
 
     void prefill(const float* embeds, int B_, int T, const int32_t* n_pad_host, const float* trailing_dev, int Tt_,
                  const float* tts_pad_dev, hipStream_t st);
+    void prefill_stack(int nB, int T, const int* npad_dev, const int* row_map, int slot_base, hipStream_t st);
+    void admit(int n_new, const int32_t* rows_host, const float* embeds, int T, const int32_t* n_pad_host, const float* trailing_dev, int Tt_,
+               const qtts_row_sampling* settings, hipStream_t st);
     void sample_talker(const qtts_sampling& sp, int eos, int min_new, int max_new, hipStream_t st);
     void frame_step(const qtts_sampling& sp, int eos, int min_new, int max_new, int64_t* codes, float* hidden,
                     int max_frames, hipStream_t st);
@@ -937,23 +952,13 @@ void qtts_talker::finalize() {
 }
 
 // ------------------------------------------------------------------------------------------ prefill
-void qtts_talker::prefill(const float* embeds, int B_, int T, const int32_t* n_pad_host, const float* trailing_dev,
-                          int Tt_, const float* tts_pad_dev, hipStream_t st) {
+// The talker's layers over the nB x T rows in pf_x (in place): the body of prefill, and of an admission, whose K/V go to the cache rows
+// row_map[i] at slots slot_base + t (attn_rows works on the local q|k|v buffer: the group is a left-padded batch of its own).
+void qtts_talker::prefill_stack(int nB, int T, const int* npad_dev, const int* row_map, int slot_base, hipStream_t st) {
     const auto& c = cfg;
-    QTTS_REQUIRE(finalized, QTTS_ERR_STATE, "talker: finalize() first");
-    QTTS_REQUIRE(B_ >= 1 && B_ <= c.max_batch, QTTS_ERR_LIMIT, "talker: batch exceeds max_batch");
-    QTTS_REQUIRE(T >= 1 && T < c.max_seq, QTTS_ERR_LIMIT, "talker: prompt longer than max_seq");
-    QTTS_REQUIRE(Tt_ >= 1, QTTS_ERR_ARG, "talker: trailing_text_hidden must have >= 1 row");
-    B = B_; T0 = T; Tt = Tt_;
-    for (int b = 0; b < B; ++b) QTTS_REQUIRE(n_pad_host[b] >= 0 && n_pad_host[b] < T, QTTS_ERR_ARG, "talker: n_pad out of range");
-    const int M = B * T, H = td.H, W = td.qd + 2 * td.kvd;
-    pf_x.ensure((size_t)M * H * 4); pf_n.ensure((size_t)M * std::max(H, td.qd) * 4); pf_qkv.ensure((size_t)M * W * 4);
+    const int M = nB * T, H = td.H, W = td.qd + 2 * td.kvd;
+    pf_n.ensure((size_t)M * std::max(H, td.qd) * 4); pf_qkv.ensure((size_t)M * W * 4);
     pf_att.ensure((size_t)M * td.qd * 4); pf_act.ensure((size_t)M * td.I * 4);
-    trailing.ensure((size_t)B * Tt * H * 4); tts_pad.ensure((size_t)H * 4);
-    QTTS_CHECK_HIP(hipMemcpyAsync(pf_x.p, embeds, (size_t)M * H * 4, hipMemcpyDeviceToDevice, st));
-    QTTS_CHECK_HIP(hipMemcpyAsync(trailing.p, trailing_dev, (size_t)B * Tt * H * 4, hipMemcpyDeviceToDevice, st));
-    QTTS_CHECK_HIP(hipMemcpyAsync(tts_pad.p, tts_pad_dev, (size_t)H * 4, hipMemcpyDeviceToDevice, st));
-    QTTS_CHECK_HIP(hipMemcpyAsync(n_pad_d.p, n_pad_host, (size_t)B * 4, hipMemcpyHostToDevice, st));
     float *xs = pf_x.as<float>(), *nb = pf_n.as<float>(), *qb = pf_qkv.as<float>(), *ab = pf_att.as<float>(), *mb = pf_act.as<float>();
     // bf16 mode (round 3): a tensor whose only consumer is a GEMM -- the normed rows, the attention output, the SwiGLU product -- is
     // written as bf16 by its producer (the GEMM rounded it the same way while staging: bit-identical results) and read at half the
@@ -976,13 +981,13 @@ void qtts_talker::prefill(const float* embeds, int B_, int T, const int32_t* n_p
         else launch_rmsnorm(xs, H, L.g1.as<float>(), td.eps, nb, H, M, H, st);
         gemm(L.qkv_r, W, H, nb, H, qb, W, ACT_NONE, nullptr);
         QkNormRopeParams q{};
-        q.qkv = qb; q.ld = W; q.B = B; q.T = T; q.nh = td.nh; q.nkv = td.nkv; q.hd = td.hd; q.qw = L.qn.as<float>();
-        q.kw = L.kn.as<float>(); q.eps = td.eps; q.inv_freq = inv_freq_t.as<float>(); q.n_pad = n_pad_d.as<int>();
-        q.kv = kv_t; q.layer = l;
+        q.qkv = qb; q.ld = W; q.B = nB; q.T = T; q.nh = td.nh; q.nkv = td.nkv; q.hd = td.hd; q.qw = L.qn.as<float>();
+        q.kw = L.kn.as<float>(); q.eps = td.eps; q.inv_freq = inv_freq_t.as<float>(); q.n_pad = npad_dev;
+        q.kv = kv_t; q.layer = l; q.row_map = row_map; q.slot_base = slot_base;
         launch_qknorm_rope_store(q, st);
         AttnRowsParams a{};
-        a.qkv = qb; a.ld = W; a.q_off = 0; a.k_off = td.qd; a.v_off = td.qd + td.kvd; a.B = B; a.T = T; a.nh = td.nh;
-        a.nkv = td.nkv; a.hd = td.hd; a.window = 0; a.n_pad = n_pad_d.as<int>(); a.out = ab; a.ldo = td.qd;
+        a.qkv = qb; a.ld = W; a.q_off = 0; a.k_off = td.qd; a.v_off = td.qd + td.kvd; a.B = nB; a.T = T; a.nh = td.nh;
+        a.nkv = td.nkv; a.hd = td.hd; a.window = 0; a.n_pad = npad_dev; a.out = ab; a.ldo = td.qd;
         if (a16) a.out16 = ab;
         launch_attn_rows(a, st);
         gemm(L.o_r, H, td.qd, ab, td.qd, xs, H, ACT_NONE, xs);
@@ -991,6 +996,26 @@ void qtts_talker::prefill(const float* embeds, int B_, int T, const int32_t* n_p
         gemm(L.gu_r, 2 * td.I, H, nb, H, mb, td.I, ACT_SWIGLU, nullptr, a16);
         gemm(L.d_r, H, td.I, mb, td.I, xs, H, ACT_NONE, xs);
     }
+}
+
+void qtts_talker::prefill(const float* embeds, int B_, int T, const int32_t* n_pad_host, const float* trailing_dev,
+                          int Tt_, const float* tts_pad_dev, hipStream_t st) {
+    const auto& c = cfg;
+    QTTS_REQUIRE(finalized, QTTS_ERR_STATE, "talker: finalize() first");
+    QTTS_REQUIRE(B_ >= 1 && B_ <= c.max_batch, QTTS_ERR_LIMIT, "talker: batch exceeds max_batch");
+    QTTS_REQUIRE(T >= 1 && T < c.max_seq, QTTS_ERR_LIMIT, "talker: prompt longer than max_seq");
+    QTTS_REQUIRE(Tt_ >= 1, QTTS_ERR_ARG, "talker: trailing_text_hidden must have >= 1 row");
+    B = B_; T0 = T; Tt = Tt_;
+    for (int b = 0; b < B; ++b) QTTS_REQUIRE(n_pad_host[b] >= 0 && n_pad_host[b] < T, QTTS_ERR_ARG, "talker: n_pad out of range");
+    const int M = B * T, H = td.H;
+    pf_x.ensure((size_t)M * H * 4);
+    trailing.ensure((size_t)B * Tt * H * 4); tts_pad.ensure((size_t)H * 4);
+    QTTS_CHECK_HIP(hipMemcpyAsync(pf_x.p, embeds, (size_t)M * H * 4, hipMemcpyDeviceToDevice, st));
+    QTTS_CHECK_HIP(hipMemcpyAsync(trailing.p, trailing_dev, (size_t)B * Tt * H * 4, hipMemcpyDeviceToDevice, st));
+    QTTS_CHECK_HIP(hipMemcpyAsync(tts_pad.p, tts_pad_dev, (size_t)H * 4, hipMemcpyDeviceToDevice, st));
+    QTTS_CHECK_HIP(hipMemcpyAsync(n_pad_d.p, n_pad_host, (size_t)B * 4, hipMemcpyHostToDevice, st));
+    prefill_stack(B, T, n_pad_d.as<int>(), nullptr, 0, st);
+    float* xs = pf_x.as<float>();
     // last position of every (left-padded) row -> final norm -> past_hidden, logits (M:1726-1740)
     for (int b = 0; b < B; ++b)
         QTTS_CHECK_HIP(hipMemcpyAsync(x.as<float>() + (size_t)b * H, xs + ((size_t)b * T + T - 1) * H, (size_t)H * 4,
@@ -1104,6 +1129,7 @@ void qtts_talker::frame_step(const qtts_sampling& sp, int eos, int min_new, int 
     e.cp_emb = emb_cp.as<float>(); e.cur_tok = cur_tok.as<int>(); e.sub = sub.as<int>(); e.sub_stride = G;
     e.trailing = trailing.as<float>(); e.Tt = Tt; e.tts_pad = tts_pad.as<float>(); e.past_hidden = past_hidden.as<float>();
     e.x_out = x.as<float>(); e.x_out16 = bf16 ? x16.as<unsigned short>() : nullptr; e.codes_out = codes; e.hidden_out = hidden; e.max_frames = max_frames; e.st = ss;
+    if (row_mode) { e.row_origin = &rows_d.as<SampleRow>()->origin; e.row_origin_stride = (int)(sizeof(SampleRow) / sizeof(int)); }
     if (!skinny_only) launch_embed_sum(e, st);
     // ---- talker decode forward (M:1706-1727)
     cur_stack = 0;
@@ -1268,8 +1294,28 @@ struct RowTable {
     int poll_from = 0x7fffffff; // no row can finish before this many tokens exist (EOS blocked and limit not reached): no poll needed earlier
     bool fast_t = true, fast_c = true;      // every row meets sample_kernel_v2's predicate, talker / subtalker half (launch_sample)
 };
-static RowTable check_rows(const qtts_talker* t, const qtts_row_sampling* rows, int n_rows, const char* who) {
+// one request's settings, checked, as the samplers read them (`b`: the row the messages name)
+static SampleRow check_row(const qtts_row_sampling& q, int b, const char* who) {
     auto fail = [&](int code, int b, const char* what) { throw Error(code, std::string(who) + ": row " + std::to_string(b) + ": " + what); };
+    if (q.max_new_tokens < 1) fail(QTTS_ERR_ARG, b, "max_new_tokens >= 1");
+    if (q.do_sample && !(q.top_p > 0.0f && q.top_p <= 1.0f)) fail(QTTS_ERR_ARG, b, "top_p must be in (0, 1]");
+    if (q.subtalker_dosample && !(q.subtalker_top_p > 0.0f && q.subtalker_top_p <= 1.0f)) fail(QTTS_ERR_ARG, b, "subtalker_top_p must be in (0, 1]");
+    if (!(q.temperature > 0.0f)) fail(QTTS_ERR_ARG, b, "temperature must be > 0");
+    if (!(q.subtalker_temperature > 0.0f)) fail(QTTS_ERR_ARG, b, "subtalker_temperature must be > 0");
+    if (q.top_k < 0 || q.subtalker_top_k < 0) fail(QTTS_ERR_ARG, b, "top_k >= 0");
+    if (!(q.repetition_penalty > 0.0f)) fail(QTTS_ERR_ARG, b, "repetition_penalty must be > 0");
+    SampleRow o;
+    memset(&o, 0, sizeof(o));
+    o.do_sample = q.do_sample ? 1 : 0; o.top_k = q.top_k; o.top_p = q.top_p; o.temperature = q.temperature;
+    o.repetition_penalty = q.repetition_penalty; o.sub_do_sample = q.subtalker_dosample ? 1 : 0; o.sub_top_k = q.subtalker_top_k;
+    o.sub_top_p = q.subtalker_top_p; o.sub_temperature = q.subtalker_temperature; o.seed = q.seed;
+    o.max_new_tokens = q.max_new_tokens; o.min_new_tokens = q.min_new_tokens;
+    return o;
+}
+// whether a row meets sample_kernel_v2's predicate, talker / subtalker half (launch_sample)
+static bool row_fast_talker(const SampleRow& o, int V) { return o.do_sample && o.top_k > 0 && o.top_k <= 64 && o.top_k < V && V <= 4096; }
+static bool row_fast_sub(const SampleRow& o, int Vc) { return o.sub_do_sample && o.sub_top_k > 0 && o.sub_top_k <= 64 && o.sub_top_k < Vc && Vc <= 4096; }
+static RowTable check_rows(const qtts_talker* t, const qtts_row_sampling* rows, int n_rows, const char* who) {
     QTTS_REQUIRE(rows, QTTS_ERR_ARG, "null argument");
     QTTS_REQUIRE(n_rows == t->B, QTTS_ERR_ARG, std::string(who) + ": n_rows (" + std::to_string(n_rows) + ") must equal the prefilled batch (" +
                                                    std::to_string(t->B) + ")");
@@ -1280,28 +1326,122 @@ static RowTable check_rows(const qtts_talker* t, const qtts_row_sampling* rows, 
     const int V = t->cfg.vocab_size, Vc = t->cfg.cp_vocab_size;
     for (int b = 0; b < n_rows; ++b) {
         const qtts_row_sampling& q = rows[b];
-        if (q.max_new_tokens < 1) fail(QTTS_ERR_ARG, b, "max_new_tokens >= 1");
-        if (q.do_sample && !(q.top_p > 0.0f && q.top_p <= 1.0f)) fail(QTTS_ERR_ARG, b, "top_p must be in (0, 1]");
-        if (q.subtalker_dosample && !(q.subtalker_top_p > 0.0f && q.subtalker_top_p <= 1.0f)) fail(QTTS_ERR_ARG, b, "subtalker_top_p must be in (0, 1]");
-        if (!(q.temperature > 0.0f)) fail(QTTS_ERR_ARG, b, "temperature must be > 0");
-        if (!(q.subtalker_temperature > 0.0f)) fail(QTTS_ERR_ARG, b, "subtalker_temperature must be > 0");
-        if (q.top_k < 0 || q.subtalker_top_k < 0) fail(QTTS_ERR_ARG, b, "top_k >= 0");
-        if (!(q.repetition_penalty > 0.0f)) fail(QTTS_ERR_ARG, b, "repetition_penalty must be > 0");
         SampleRow& o = r.tab[b];
-        memset(&o, 0, sizeof(o));
-        o.do_sample = q.do_sample ? 1 : 0; o.top_k = q.top_k; o.top_p = q.top_p; o.temperature = q.temperature;
-        o.repetition_penalty = q.repetition_penalty; o.sub_do_sample = q.subtalker_dosample ? 1 : 0; o.sub_top_k = q.subtalker_top_k;
-        o.sub_top_p = q.subtalker_top_p; o.sub_temperature = q.subtalker_temperature; o.seed = q.seed;
-        o.max_new_tokens = q.max_new_tokens; o.min_new_tokens = q.min_new_tokens;
+        o = check_row(q, b, who);
         r.max_new = std::max(r.max_new, (int)q.max_new_tokens);
         r.poll_from = std::min(r.poll_from, std::min((int)q.min_new_tokens, (int)q.max_new_tokens - 1));
-        r.fast_t = r.fast_t && o.do_sample && o.top_k > 0 && o.top_k <= 64 && o.top_k < V && V <= 4096;
-        r.fast_c = r.fast_c && o.sub_do_sample && o.sub_top_k > 0 && o.sub_top_k <= 64 && o.sub_top_k < Vc && Vc <= 4096;
+        r.fast_t = r.fast_t && row_fast_talker(o, V);
+        r.fast_c = r.fast_c && row_fast_sub(o, Vc);
     }
     if (t->T0 + r.max_new > t->cfg.max_seq)
         throw Error(QTTS_ERR_LIMIT, std::string(who) + ": prompt + the largest max_new_tokens of the table (" + std::to_string(r.max_new) + ") exceeds max_seq");
     return r;
 }
+// ------------------------------------------------------------------------------------------ admission into a running stream
+// A new request takes a finished row while the others keep running.  The stream has ONE position, kv_len: the group's prompts (n_new x T,
+// left-padded inside T) are prefilled as a batch of their own and their K/V stored into the rows' slots [kv_len - T, kv_len); with
+// n_pad[row] = kv_len - (the prompt's length) the row then looks like a request that was left-padded that far -- the decode attention is
+// unchanged, the previous occupant's K/V lie below n_pad.  The row's table entry gets origin = the stream's step count, from which the
+// samplers and the embedding sum count the occupant's own tokens, frames and Philox steps.  Runs on the engine's stream between two
+// stream_step calls; every check comes before the first write, so a refused call changes nothing.
+void qtts_talker::admit(int n_new, const int32_t* rows_host, const float* embeds, int T, const int32_t* n_pad_host, const float* trailing_dev, int Tt_,
+                        const qtts_row_sampling* settings, hipStream_t st) {
+    const char* who = "stream_admit";
+    auto& g = sg;
+    auto fail = [&](int code, int b, const std::string& what) { throw Error(code, std::string(who) + ": row " + std::to_string(b) + ": " + what); };
+    QTTS_REQUIRE(n_new >= 1 && n_new <= B, QTTS_ERR_ARG, "stream_admit: 1 <= n_new <= the stream's rows");
+    QTTS_REQUIRE(T >= 1 && Tt_ >= 1, QTTS_ERR_ARG, "stream_admit: T >= 1 and >= 1 trailing row");
+    int fin[6];
+    std::vector<int> uf(B);
+    QTTS_CHECK_HIP(hipMemcpyAsync(fin, ss.n_generated, sizeof(fin), hipMemcpyDeviceToHost, st));
+    QTTS_CHECK_HIP(hipMemcpyAsync(uf.data(), ss.unfinished, (size_t)B * 4, hipMemcpyDeviceToHost, st));
+    QTTS_CHECK_HIP(hipStreamSynchronize(st));
+    check_fused_flag(fin[5], who);
+    const int gen_step = fin[1], kv_len = fin[2];
+    std::vector<SampleRow> entries(n_new);
+    std::vector<int> npad_g(n_new);
+    std::vector<char> seen(B, 0);
+    for (int i = 0; i < n_new; ++i) {
+        const int b = rows_host[i];
+        QTTS_REQUIRE(b >= 0 && b < B, QTTS_ERR_ARG, std::string(who) + ": row " + std::to_string(b) + " is not a row of this stream (" + std::to_string(B) + " rows)");
+        if (seen[b]) fail(QTTS_ERR_ARG, b, "listed twice");
+        seen[b] = 1;
+        if (uf[b]) fail(QTTS_ERR_ARG, b, "its occupant is still unfinished");
+        QTTS_REQUIRE(n_pad_host[i] >= 0 && n_pad_host[i] < T, QTTS_ERR_ARG, std::string(who) + ": row " + std::to_string(b) + ": n_pad out of range");
+        entries[i] = check_row(settings[i], b, who);
+        if (T - n_pad_host[i] > kv_len)
+            fail(QTTS_ERR_LIMIT, b, "the prompt (" + std::to_string(T - n_pad_host[i]) + " rows) is longer than the stream's position (" + std::to_string(kv_len) + ")");
+        if (kv_len + settings[i].max_new_tokens > cfg.max_seq)
+            fail(QTTS_ERR_LIMIT, b, "the stream's position (" + std::to_string(kv_len) + ") + max_new_tokens (" + std::to_string(settings[i].max_new_tokens) + ") exceeds max_seq");
+        if (settings[i].max_new_tokens > g.max_row)
+            fail(QTTS_ERR_LIMIT, b, "max_new_tokens (" + std::to_string(settings[i].max_new_tokens) + ") exceeds the stream's max_row_tokens (" + std::to_string(g.max_row) + ")");
+        if (Tt_ > Tt) fail(QTTS_ERR_LIMIT, b, "trailing rows (" + std::to_string(Tt_) + ") exceed the stream's trailing capacity (" + std::to_string(Tt) + ")");
+        entries[i].origin = gen_step;
+        npad_g[i] = kv_len - T + n_pad_host[i];
+    }
+    if (T > kv_len)       // (every prompt fits, the group's padded length does not)
+        fail(QTTS_ERR_LIMIT, rows_host[0], "the group's padded length T (" + std::to_string(T) + ") is longer than the stream's position (" + std::to_string(kv_len) + ")");
+    // ---- from here on the call writes
+    const int H = td.H, V = cfg.vocab_size, M = n_new * T, base = kv_len - T;
+    bool fast_t = row_fast_t, fast_c = row_fast_c;
+    for (auto& e : entries) { fast_t = fast_t && row_fast_talker(e, V); fast_c = fast_c && row_fast_sub(e, cfg.cp_vocab_size); }
+    if (fast_t != row_fast_t || fast_c != row_fast_c) {      // an occupant outside the fast samplers' class: the stream's frame graphs bake the class in
+        row_fast_t = fast_t; row_fast_c = fast_c;
+        destroy_graph(); graph_nodes = 0;
+        graph_key.row_fast_t = row_fast_t; graph_key.row_fast_c = row_fast_c;
+    }
+    pf_x.ensure((size_t)M * H * 4);
+    adm_rows_d.ensure((size_t)64 * 4); adm_npad_d.ensure((size_t)64 * 4);
+    adm_x.ensure((size_t)n_new * H * 4); adm_ph.ensure((size_t)n_new * H * 4); adm_lg.ensure((size_t)n_new * V * 4);
+    QTTS_CHECK_HIP(hipMemcpyAsync(pf_x.p, embeds, (size_t)M * H * 4, hipMemcpyDeviceToDevice, st));
+    QTTS_CHECK_HIP(hipMemcpyAsync(adm_rows_d.p, rows_host, (size_t)n_new * 4, hipMemcpyHostToDevice, st));
+    QTTS_CHECK_HIP(hipMemcpyAsync(adm_npad_d.p, n_pad_host, (size_t)n_new * 4, hipMemcpyHostToDevice, st));
+    prefill_stack(n_new, T, adm_npad_d.as<int>(), adm_rows_d.as<int>(), base, st);
+    // last position of every prompt -> final norm -> past_hidden, logits: computed on staging rows, then copied to the rows admitted into
+    const float* xs = pf_x.as<float>();
+    for (int i = 0; i < n_new; ++i)
+        QTTS_CHECK_HIP(hipMemcpyAsync(adm_x.as<float>() + (size_t)i * H, xs + ((size_t)i * T + T - 1) * H, (size_t)H * 4, hipMemcpyDeviceToDevice, st));
+    launch_rmsnorm(adm_x.as<float>(), H, t_norm.as<float>(), td.eps, adm_ph.as<float>(), H, n_new, H, st);
+    SkinnyParams h{};
+    h.x = adm_ph.as<float>(); h.ldx = H; h.M = n_new; h.Wp = head_p.p; h.N = V; h.K = H;
+    h.out = adm_lg.as<float>(); h.ldo = V; h.act = ACT_NONE; h.fs = fs_head;
+    launch_skinny(h, bf16, st);
+    const int zero = 0, one = 1;
+    for (int i = 0; i < n_new; ++i) {
+        const int b = rows_host[i];
+        QTTS_CHECK_HIP(hipMemcpyAsync(past_hidden.as<float>() + (size_t)b * H, adm_ph.as<float>() + (size_t)i * H, (size_t)H * 4, hipMemcpyDeviceToDevice, st));
+        QTTS_CHECK_HIP(hipMemcpyAsync(logits.as<float>() + (size_t)b * V, adm_lg.as<float>() + (size_t)i * V, (size_t)V * 4, hipMemcpyDeviceToDevice, st));
+        // the occupant's trailing text, right-padded with tts_pad to the stream's capacity
+        float* tr = trailing.as<float>() + (size_t)b * Tt * H;
+        QTTS_CHECK_HIP(hipMemcpyAsync(tr, trailing_dev + (size_t)i * Tt_ * H, (size_t)Tt_ * H * 4, hipMemcpyDeviceToDevice, st));
+        for (int j = Tt_; j < Tt; ++j)
+            QTTS_CHECK_HIP(hipMemcpyAsync(tr + (size_t)j * H, tts_pad.p, (size_t)H * 4, hipMemcpyDeviceToDevice, st));
+        QTTS_CHECK_HIP(hipMemcpyAsync(n_pad_d.as<int>() + b, &npad_g[i], 4, hipMemcpyHostToDevice, st));
+        QTTS_CHECK_HIP(hipMemcpyAsync(rows_d.as<SampleRow>() + b, &entries[i], sizeof(SampleRow), hipMemcpyHostToDevice, st));
+        QTTS_CHECK_HIP(hipMemcpyAsync(ss.unfinished + b, &one, 4, hipMemcpyHostToDevice, st));
+    }
+    QTTS_CHECK_HIP(hipMemcpyAsync(ss.done, &zero, 4, hipMemcpyHostToDevice, st));
+    // token 0 of the admitted rows only: the talker's sampler on ONE row at a time (every per-row pointer moved to the row; the table's
+    // Philox counter has no row term).  With the step count as the token count the row's own count is 0; the stream's counters do not move.
+    for (int i = 0; i < n_new; ++i) {
+        const int b = rows_host[i];
+        SampleParams p{};
+        p.logits = logits.as<float>() + (size_t)b * V; p.ld = V; p.V = V; p.B = 1;
+        p.generated = generated.as<int>() + (size_t)b * gen_cap; p.gen_stride = gen_cap; p.n_generated_dev = ss.gen_step;
+        p.repetition_penalty = 1.0f; p.eos = g.eos; p.min_new_tokens = 0;
+        p.suppress_mask = suppress.as<unsigned char>();
+        p.seed_dev = seed_d.as<unsigned long long>(); p.stream_id = 0; p.step_dev = ss.gen_step;
+        p.tok_out = cur_tok.as<int>() + b; p.tok_stride = 1; p.unfinished = ss.unfinished + b; p.generated_out = generated.as<int>() + (size_t)b * gen_cap;
+        p.max_new_tokens = g.max_new; p.done_in = ss.done;
+        p.rows = rows_d.as<SampleRow>() + b; p.rows_sub = 0; p.rows_fast = row_fast_t;
+        launch_sample(p, st);
+    }
+    QTTS_CHECK_HIP(hipStreamSynchronize(st));      // (host buffers above must outlive the copies)
+    for (int i = 0; i < n_new; ++i) g.tab[rows_host[i]] = entries[i];
+    g.done = 0;
+    admit_calls += 1; admitted_rows += n_new;
+}
+
 // What every generation call does before its first sample: the suppress mask and the Philox key -- or the table -- go to the device,
 // the token history is sized.  Consumes the prefill.
 static void upload_call_state(qtts_talker* t, const qtts_sampling& sp, const RowTable* rt, int max_new, const int32_t* suppress_host, int n_suppress,
@@ -1464,8 +1604,7 @@ static void stream_launch_frames(qtts_talker* t, int n, hipStream_t st) {
         QTTS_CHECK_HIP(hipMemcpyAsync(&g.done, t->ss.done, 4, hipMemcpyDeviceToHost, st));
         QTTS_CHECK_HIP(hipStreamSynchronize(st));
     };
-    const int total = g.max_new - 1;
-    int left = std::min(n, total - g.launched);
+    int left = std::min(n, g.total - g.launched);
     while (!g.done && left > 0) {
         if (!use_graph) {
             t->set_attn_mode(t->T0 + g.launched + 1);
@@ -1484,14 +1623,23 @@ static void stream_launch_frames(qtts_talker* t, int n, hipStream_t st) {
 }
 
 // The body of qtts_talker_stream_begin and qtts_talker_stream_begin_rows (`rt`: as in generate_body).
+// `max_row` > 0: an admitting stream.  A row's outputs and history then hold max_row tokens of ONE occupant, and the stream itself has no
+// token limit of its own: its stop condition is "no row unfinished" (every row has its own limit), its length is bounded by the positions
+// (max_seq), which every admission checks for its own rows.
 static void stream_begin_body(qtts_talker* t, const qtts_sampling* sp, const RowTable* rt, int32_t max_new_tokens, int32_t min_new_tokens,
                               int32_t eos_token_id, const int32_t* suppress_host, int32_t n_suppress, int64_t* codes_dev,
-                              float* hidden_dev, hipStream_t st) {
-    upload_call_state(t, *sp, rt, max_new_tokens, suppress_host, n_suppress, st);
+                              float* hidden_dev, hipStream_t st, int max_row = 0) {
+    upload_call_state(t, *sp, rt, max_row > 0 ? max_row : max_new_tokens, suppress_host, n_suppress, st);
     auto& g = t->sg;
     g = qtts_talker::StreamGen{};
     g.sp = *sp; g.eos = eos_token_id; g.min_new = min_new_tokens; g.max_new = max_new_tokens;
     g.max_frames = std::max(1, max_new_tokens - 1); g.codes = codes_dev; g.hidden = hidden_dev;
+    g.total = max_new_tokens - 1; g.st = st;
+    if (max_row > 0) {
+        g.admitting = true; g.max_row = max_row; g.tab = rt->tab;
+        g.max_new = t->cfg.max_seq; g.max_frames = std::max(1, max_row - 1); g.total = t->cfg.max_seq - t->T0 - 1;
+    }
+    t->admit_calls = 0; t->admitted_rows = 0;
     t->frames_run = 0;
     t->sample_talker(*sp, eos_token_id, min_new_tokens, max_new_tokens, st);      // token 0
     QTTS_CHECK_HIP(hipMemcpyAsync(&g.done, t->ss.done, 4, hipMemcpyDeviceToHost, st));
@@ -1532,6 +1680,61 @@ int qtts_talker_stream_begin_rows(qtts_talker* t, const qtts_row_sampling* rows_
     QTTS_API_END
 }
 
+int qtts_talker_stream_begin_admitting(qtts_talker* t, const qtts_row_sampling* rows_host, int32_t n_rows, int32_t max_row_tokens,
+                                       int32_t eos_token_id, const int32_t* suppress_host, int32_t n_suppress, int64_t* codes_dev,
+                                       float* hidden_dev, void* stream) {
+    QTTS_API_BEGIN
+    QTTS_REQUIRE(t && rows_host && codes_dev, QTTS_ERR_ARG, "null argument");
+    QTTS_REQUIRE(t->prefilled, QTTS_ERR_STATE, "stream_begin_admitting: prefill() first");
+    QTTS_REQUIRE(!t->profile, QTTS_ERR_STATE, "stream_begin_admitting: not available in profile mode");
+    QTTS_REQUIRE(eos_token_id >= 0 && eos_token_id < t->cfg.vocab_size, QTTS_ERR_ARG, "eos_token_id");
+    QTTS_REQUIRE(max_row_tokens >= 1, QTTS_ERR_ARG, "stream_begin_admitting: max_row_tokens >= 1");
+    const RowTable rt = check_rows(t, rows_host, n_rows, "stream_begin_admitting");
+    for (int b = 0; b < n_rows; ++b)
+        if (rows_host[b].max_new_tokens > max_row_tokens)
+            throw Error(QTTS_ERR_LIMIT, "stream_begin_admitting: row " + std::to_string(b) + ": max_new_tokens (" + std::to_string(rows_host[b].max_new_tokens) +
+                                            ") exceeds max_row_tokens (" + std::to_string(max_row_tokens) + ")");
+    const qtts_sampling none{};
+    stream_begin_body(t, &none, &rt, rt.max_new, rt.poll_from, eos_token_id, suppress_host, n_suppress, codes_dev, hidden_dev, (hipStream_t)stream,
+                      max_row_tokens);
+    QTTS_API_END
+}
+
+int qtts_talker_stream_admit(qtts_talker* t, int32_t n_new, const int32_t* rows_host, const float* embeds_dev, int32_t T, const int32_t* n_pad_host,
+                             const float* trailing_dev, int32_t Tt, const qtts_row_sampling* settings_host, void* stream) {
+    QTTS_API_BEGIN
+    QTTS_REQUIRE(t && rows_host && embeds_dev && n_pad_host && trailing_dev && settings_host, QTTS_ERR_ARG, "null argument");
+    QTTS_REQUIRE(t->sg.active && t->sg.admitting, QTTS_ERR_STATE, "stream_admit: no admitting stream is open (qtts_talker_stream_begin_admitting first)");
+    t->admit(n_new, rows_host, embeds_dev, T, n_pad_host, trailing_dev, Tt, settings_host, (hipStream_t)stream);
+    QTTS_API_END
+}
+
+int qtts_talker_stream_rows(qtts_talker* t, int32_t* unfinished_host, int32_t* frames_host, int32_t* kv_len_host) {
+    QTTS_API_BEGIN
+    QTTS_REQUIRE(t && unfinished_host && frames_host && kv_len_host, QTTS_ERR_ARG, "null argument");
+    QTTS_REQUIRE(t->sg.active, QTTS_ERR_STATE, "stream_rows: no stream is open");
+    auto& g = t->sg;
+    const int B = t->B, cap = t->gen_cap;
+    int fin[6];
+    std::vector<int> uf(B), h((size_t)B * cap);
+    QTTS_CHECK_HIP(hipMemcpyAsync(fin, t->ss.n_generated, sizeof(fin), hipMemcpyDeviceToHost, g.st));
+    QTTS_CHECK_HIP(hipMemcpyAsync(uf.data(), t->ss.unfinished, (size_t)B * 4, hipMemcpyDeviceToHost, g.st));
+    QTTS_CHECK_HIP(hipMemcpyAsync(h.data(), t->generated.p, h.size() * 4, hipMemcpyDeviceToHost, g.st));
+    QTTS_CHECK_HIP(hipStreamSynchronize(g.st));
+    for (int b = 0; b < B; ++b) {
+        // the occupant's tokens so far; its frames end before its first eos (a row that reached its limit received eos there), and the
+        // frame of its newest token has not run yet
+        const int org = t->row_mode && g.admitting ? g.tab[b].origin : 0;
+        const int n_row = std::max(0, std::min(fin[0] - org, cap));
+        int e = 0;
+        while (e < n_row && h[(size_t)b * cap + e] != g.eos) ++e;
+        unfinished_host[b] = uf[b] ? 1 : 0;
+        frames_host[b] = e < n_row ? e : std::min(std::max(0, n_row - 1), g.max_frames);
+    }
+    *kv_len_host = fin[2];
+    QTTS_API_END
+}
+
 int qtts_talker_stream_step(qtts_talker* t, int32_t max_frames_now, int32_t* frames_total_host, int32_t* finished_host,
                             void* stream) {
     QTTS_API_BEGIN
@@ -1546,10 +1749,12 @@ int qtts_talker_stream_step(qtts_talker* t, int32_t max_frames_now, int32_t* fra
     copy_on_stream(fin, t->ss.n_generated, sizeof(fin), hipMemcpyDeviceToHost, st);
     if (fin[5]) g.active = false;                        // (no packet of a burst that lost a fused launch is handed out)
     t->check_fused_flag(fin[5], "stream_step");
+    // (an admitting stream: launches behind the latch did nothing and an admission lifts the latch -- the device's step count is the truth)
+    if (g.admitting) g.launched = fin[1];
     // frames whose codes are final: every launched step that ran before the latch; after the latch exactly final_count - 1
     const int valid = fin[3] ? fin[4] - 1 : g.launched;
     *frames_total_host = std::min(valid, g.launched);
-    *finished_host = (fin[3] || g.launched >= g.max_new - 1) ? 1 : 0;
+    *finished_host = (fin[3] || g.launched >= g.total) ? 1 : 0;
     QTTS_API_END
 }
 
@@ -1568,13 +1773,13 @@ int qtts_talker_stream_end(qtts_talker* t, int64_t* tokens_dev, int32_t* n_frame
     // an abandoned stream (ended before the stop condition) reports the frames produced so far
     const int n_tok = fin[3] ? fin[4] : fin[0];
     *n_frames_host = std::min(std::max(0, n_tok - 1), g.launched);
-    if (tokens_dev) {
-        const int B = t->B, cap = g.max_new;
+    if (tokens_dev) {        // (an admitting stream: (B, max_row_tokens), every row's CURRENT occupant)
+        const int B = t->B, cap = g.admitting ? g.max_row : g.max_new;
         std::vector<int> h((size_t)B * cap);
         copy_on_stream(h.data(), t->generated.p, h.size() * 4, hipMemcpyDeviceToHost, st);
         std::vector<int64_t> w(h.size(), -1);
         for (int b = 0; b < B; ++b)
-            for (int i = 0; i < n_tok && i < cap; ++i) w[(size_t)b * cap + i] = h[(size_t)b * cap + i];
+            for (int i = 0; i < n_tok - (g.admitting ? g.tab[b].origin : 0) && i < cap; ++i) w[(size_t)b * cap + i] = h[(size_t)b * cap + i];
         copy_on_stream(tokens_dev, w.data(), w.size() * 8, hipMemcpyHostToDevice, st);
     }
     QTTS_API_END
@@ -1630,6 +1835,7 @@ int qtts_talker_get_stats(qtts_talker* t, qtts_talker_stats* out) {
     out->cp_layer_per_step = t->cp_fused_slot ? t->cp_layer_per_step : 0;
     out->ks_split_per_step = t->ks_split_env ? t->ks_split_per_step : 0; out->attn_gq_per_step = t->attn_gq_per_step;
     out->graph_captures = t->graph_captures; out->row_table_last = t->row_mode ? 1 : 0;
+    out->admit_calls = (int32_t)t->admit_calls; out->admitted_rows = (int32_t)t->admitted_rows;
     QTTS_API_END
 }
 int qtts_talker_get_gemm_profile(qtts_talker* t, qtts_gemm_class* out, int32_t cap, int32_t* n) {

@@ -310,6 +310,15 @@ class Qwen3TTSForConditionalGeneration:
         # counter is (step, row-in-wave, codebook)).  With one (the per-row table, whose counter has no row term) every request needs a
         # seed of its own: a seed sequence is per request and is only sliced; ONE integer s gives request i of the call s + i,
         # whichever wave it lands in; no seed at all leaves every row to draw a fresh one (`TalkerEngine._row_table`).
+        schedule = kwargs.get("schedule", "waves")
+        if schedule not in ("waves", "refill"):
+            raise ValueError(f"`schedule` must be 'waves' or 'refill', but is {schedule!r}")
+        if schedule == "refill":
+            # the whole request list goes to the engine, which admits queued requests into rows as they finish (`TalkerEngine.generate`)
+            out = self.talker.generate(embeds, mask, trailing, pad, min_new_tokens=2,
+                                       eos_token_id=eos_token_id if eos_token_id is not None else c.codec_eos_token_id,
+                                       suppress_tokens=suppress, seed=seed, schedule="refill", **knobs)
+            return self._trim_at_eos(out, codes_all, hidden_all)
         per_request = any(_is_row_seq(v) for v in knobs.values()) or _is_row_seq(seed)
         if per_request:
             seeds = list(seed) if _is_row_seq(seed) else ([int(seed) + i for i in range(n_req)] if seed is not None else [None] * n_req)
@@ -324,12 +333,17 @@ class Qwen3TTSForConditionalGeneration:
                                        eos_token_id=eos_token_id if eos_token_id is not None else c.codec_eos_token_id,
                                        suppress_tokens=suppress,
                                        seed=seeds[sl] if per_request else base_seed + b0 // mb, **wave)
-            first = out.codes[:, :, 0]
-            stop = first == c.codec_eos_token_id                                                           # M:2283-2289
-            for i in range(first.shape[0]):
-                n_eff = int(torch.argmax(stop[i].int())) if bool(stop[i].any()) else first.shape[1]
-                codes_all.append(out.codes[i, :n_eff])
-                hidden_all.append(out.hidden[i, :n_eff] if out.hidden is not None else None)
+            self._trim_at_eos(out, codes_all, hidden_all)
+        return codes_all, hidden_all
+
+    def _trim_at_eos(self, out, codes_all, hidden_all):
+        """Every request's frames up to its first eos in codebook 0 (M:2283-2289), appended to the two lists."""
+        first = out.codes[:, :, 0]
+        stop = first == self.config.codec_eos_token_id
+        for i in range(first.shape[0]):
+            n_eff = int(torch.argmax(stop[i].int())) if bool(stop[i].any()) else first.shape[1]
+            codes_all.append(out.codes[i, :n_eff])
+            hidden_all.append(out.hidden[i, :n_eff] if out.hidden is not None else None)
         return codes_all, hidden_all
 
 

@@ -296,6 +296,11 @@ class TalkerEngine:
         fused launches for good, so the request is re-run ONCE here on the separate launches instead of surfacing a bare error.
         (`generate_stream` cannot do that after it has yielded packets: there the error reaches the caller, whose retry runs on the
         separate launches.)"""
+        schedule = kw.pop("schedule", "waves")
+        if schedule == "refill":
+            return self._generate_refill(*args, **kw)
+        if schedule != "waves":
+            raise ValueError(f"`schedule` must be 'waves' or 'refill', but is {schedule!r}")
         giveups = self.stats()["cp_fused_giveups"]
         try:
             return self._generate_once(*args, **kw)
@@ -520,6 +525,182 @@ class TalkerEngine:
                 with torch.cuda.device(dev), torch.cuda.stream(self._stream):
                     _lib.check(self._lib.qtts_talker_stream_end(self._h, None, C.byref(nf), self._s()))
                 torch.cuda.current_stream(dev).wait_stream(self._stream)
+
+    # ------------------------------------------------------------------ admission into finished rows (include/qtts.h, ABI v15)
+    @_lib.locked
+    def stream_open(self, inputs_embeds: torch.Tensor, n_pad: List[int], trailing_text_hidden: torch.Tensor, tts_pad_embed: torch.Tensor,
+                    rows, max_row_tokens: int, eos_token_id: int, suppress_tokens: List[int], output_hidden_states: bool = False):
+        """Prefill + `qtts_talker_stream_begin_admitting`: `rows` is a `_lib.RowSamplingC` array with one entry per row of
+        `inputs_embeds` (B, T, H; row b left-padded by n_pad[b]).  Returns (codes (B, max_row_tokens - 1, G), hidden or None): the
+        blocks the stream fills, ONE occupant per row at a time -- copy a finished row out before `stream_admit` re-uses it."""
+        c, dev = self.config, self.device
+        B, T, H = inputs_embeds.shape
+        if B > self.max_batch:
+            raise ValueError(f"batch {B} exceeds max_batch {self.max_batch} given at construction")
+        self._live_batch = int(B)
+        emb = inputs_embeds.to(dev, torch.float32).contiguous()
+        trail = trailing_text_hidden.to(dev, torch.float32).contiguous()
+        pad = tts_pad_embed.to(dev, torch.float32).reshape(-1).contiguous()
+        F = max(1, int(max_row_tokens) - 1)
+        codes = torch.zeros(B, F, c.num_code_groups, dtype=torch.int64, device=dev)
+        hidden = torch.zeros(B, F, H, dtype=torch.float32, device=dev) if output_hidden_states else None
+        npad_c = (C.c_int32 * B)(*[int(x) for x in n_pad])
+        sup_c = (C.c_int32 * max(1, len(suppress_tokens)))(*[int(x) for x in suppress_tokens])
+        self._stream.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.device(dev), torch.cuda.stream(self._stream):
+            _lib.check(self._lib.qtts_talker_prefill(self._h, C.c_void_p(emb.data_ptr()), B, T, npad_c, C.c_void_p(trail.data_ptr()),
+                                                     trail.shape[1], C.c_void_p(pad.data_ptr()), self._s()))
+            _lib.check(self._lib.qtts_talker_stream_begin_admitting(
+                self._h, rows, B, int(max_row_tokens), int(eos_token_id), sup_c, len(suppress_tokens), C.c_void_p(codes.data_ptr()),
+                C.c_void_p(hidden.data_ptr()) if hidden is not None else None, self._s()))
+        self._open = (codes, hidden)          # (the stream writes these blocks until `stream_close`)
+        return codes, hidden
+
+    @_lib.locked
+    def stream_admit(self, row_ids: List[int], inputs_embeds: torch.Tensor, n_pad: List[int], trailing_text_hidden: torch.Tensor, rows):
+        """`qtts_talker_stream_admit`: request i of the group (inputs_embeds (n, T', H) left-padded by n_pad[i], trailing (n, Tt', H),
+        settings rows[i]) takes the finished row row_ids[i] of the open stream."""
+        dev = self.device
+        n, T, H = inputs_embeds.shape
+        emb = inputs_embeds.to(dev, torch.float32).contiguous()
+        trail = trailing_text_hidden.to(dev, torch.float32).contiguous()
+        ids_c = (C.c_int32 * n)(*[int(x) for x in row_ids])
+        npad_c = (C.c_int32 * n)(*[int(x) for x in n_pad])
+        self._stream.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.device(dev), torch.cuda.stream(self._stream):
+            _lib.check(self._lib.qtts_talker_stream_admit(self._h, n, ids_c, C.c_void_p(emb.data_ptr()), T, npad_c,
+                                                          C.c_void_p(trail.data_ptr()), trail.shape[1], rows, self._s()))
+
+    @_lib.locked
+    def stream_rows(self):
+        """`qtts_talker_stream_rows`: (unfinished[B], final frames[B] of each row's occupant, the stream's position kv_len)."""
+        B = self._live_batch
+        uf, fr, kv = (C.c_int32 * B)(), (C.c_int32 * B)(), C.c_int32(0)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.qtts_talker_stream_rows(self._h, uf, fr, C.byref(kv)))
+        return list(uf), list(fr), int(kv.value)
+
+    @_lib.locked
+    def stream_step(self, max_frames_now: int):
+        """`qtts_talker_stream_step` on the open stream: (frame steps the stream has run, whether its stop condition has latched)."""
+        total, fin = C.c_int32(0), C.c_int32(0)
+        with torch.cuda.device(self.device), torch.cuda.stream(self._stream):
+            _lib.check(self._lib.qtts_talker_stream_step(self._h, int(max_frames_now), C.byref(total), C.byref(fin), self._s()))
+        return int(total.value), bool(fin.value)
+
+    @_lib.locked
+    def stream_close(self, tokens: Optional[torch.Tensor] = None) -> int:
+        """`qtts_talker_stream_end`; returns the frame steps the stream ran.  `tokens`: optional int64 (B, max_row_tokens) device block
+        that receives the codebook-0 tokens of every row's current occupant (-1 behind them)."""
+        nf = C.c_int32(0)
+        with torch.cuda.device(self.device), torch.cuda.stream(self._stream):
+            _lib.check(self._lib.qtts_talker_stream_end(self._h, C.c_void_p(tokens.data_ptr()) if tokens is not None else None,
+                                                        C.byref(nf), self._s()))
+        torch.cuda.current_stream(self.device).wait_stream(self._stream)
+        self._open = None
+        return int(nf.value)
+
+    def _generate_refill(self, inputs_embeds: torch.Tensor, attention_mask: torch.Tensor, trailing_text_hidden: torch.Tensor,
+                         tts_pad_embed: torch.Tensor, max_new_tokens=2048, min_new_tokens=2, do_sample=True, top_k=50, top_p=1.0,
+                         temperature=0.9, subtalker_dosample=True, subtalker_top_k=50, subtalker_top_p=1.0, subtalker_temperature=0.9,
+                         eos_token_id: Optional[int] = None, repetition_penalty=1.05, suppress_tokens: Optional[List[int]] = None,
+                         output_hidden_states: bool = True, seed=None, packet_frames: int = 4, **unused) -> TalkerGenerateOutput:
+        """`generate(..., schedule="refill")`: any number of requests on `max_batch` rows.  The rows start with the requests of the
+        longest prompts; the stream runs in packets of `packet_frames` frames; after each packet the finished rows are retired (their
+        frames copied out, cut at the first eos in codebook 0) and every queued request that fits -- prompt no longer than the stream's
+        position, position + its limit inside max_seq -- is admitted, longest prompt first, in one `stream_admit`.  When requests remain
+        but none fits and every row has finished, the stream ends and a fresh one begins with the remainder.  Always runs on the per-row
+        table (scalars are broadcast; seeds as in `_row_table`: a list is per request, one integer s gives request i the seed s + i, none
+        draws fresh ones), so a request's codes do not depend on when or where it was admitted.  Returns the requests in the order
+        given, in `generate`'s structure: codes (N, F, G) with eos in codebook 0 behind a request's last frame, tokens (N, F + 1)."""
+        c, dev = self.config, self.device
+        if inputs_embeds.dim() != 3 or inputs_embeds.shape[-1] != c.hidden_size:
+            raise ValueError(f"inputs_embeds must be (B, T, {c.hidden_size})")
+        N, T, H = inputs_embeds.shape
+        if packet_frames < 1:
+            raise ValueError("packet_frames must be >= 1")
+        mask = attention_mask.to("cpu", torch.long)
+        n_pad = (1 - mask).sum(-1)
+        if mask.shape != (N, T) or not torch.equal(mask, (torch.arange(T)[None, :] >= n_pad[:, None]).long()) or int(n_pad.max()) >= T:
+            raise ValueError("attention_mask must be (B, T), left-padded: [0]*n_pad + [1]*(T-n_pad) per row")
+        lens = [T - int(x) for x in n_pad]
+        if not _is_row_seq(seed):
+            seed = [int(seed) + i for i in range(N)] if seed is not None else [None] * N
+        rows, _ = self._row_table(N, 0, do_sample=do_sample, top_k=top_k, top_p=top_p, temperature=temperature,
+                                  repetition_penalty=repetition_penalty, subtalker_dosample=subtalker_dosample,
+                                  subtalker_top_k=subtalker_top_k, subtalker_top_p=subtalker_top_p,
+                                  subtalker_temperature=subtalker_temperature, max_new_tokens=max_new_tokens,
+                                  min_new_tokens=min_new_tokens, seed=seed)
+        for i in range(N):           # a request's limit inside the capacity its own prompt leaves (`_clamp_new_tokens`)
+            rows[i].max_new_tokens = self._clamp_new_tokens(lens[i], int(rows[i].max_new_tokens))
+        eos = c.codec_eos_token_id if eos_token_id is None else int(eos_token_id)
+        suppress_tokens = list(suppress_tokens or [])
+        emb = inputs_embeds.to(dev, torch.float32)
+        trail = trailing_text_hidden.to(dev, torch.float32)
+        if trail.dim() != 3 or trail.shape[0] != N or trail.shape[2] != H or trail.shape[1] < 1:
+            raise ValueError("trailing_text_hidden must be (B, Tt >= 1, H)")
+        pad = tts_pad_embed.to(dev, torch.float32).reshape(-1)
+        if pad.numel() != H:
+            raise ValueError("tts_pad_embed must have H elements")
+        G, mb = c.num_code_groups, self.max_batch
+        max_row = max(int(rows[i].max_new_tokens) for i in range(N))
+        out_codes, out_hidden = [None] * N, [None] * N
+        queue = sorted(range(N), key=lambda i: (-lens[i], i))
+        st = dict(streams=0, admit_calls=0, admitted_rows=0, frames_run=0, row_frames=0, graph_captures=0)
+        caps0 = self.stats()["graph_captures"]
+
+        def group(idx):
+            Tg = max(lens[i] for i in idx)
+            tab = (_lib.RowSamplingC * len(idx))(*[rows[i] for i in idx])
+            return emb[idx][:, T - Tg:], [Tg - lens[i] for i in idx], trail[idx], tab
+
+        while queue:
+            # a fresh stream: the longest prompt first, then the longest of the rest whose limits fit behind it
+            T0 = lens[queue[0]]
+            first = [i for i in queue if T0 + int(rows[i].max_new_tokens) <= self.max_seq][:mb]
+            queue = [i for i in queue if i not in first]
+            e, npd, tr, tab = group(first)
+            codes, hidden = self.stream_open(e, npd, tr, pad, tab, max_row, eos, suppress_tokens, output_hidden_states)
+            st["streams"] += 1
+            slot = list(first)
+            try:
+                while any(r is not None for r in slot):
+                    self.stream_step(packet_frames)
+                    unfinished, frames, kv_len = self.stream_rows()
+                    for b, r in enumerate(slot):
+                        if r is not None and not unfinished[b]:
+                            out_codes[r] = codes[b, :frames[b]].clone()
+                            out_hidden[r] = hidden[b, :frames[b]].clone() if hidden is not None else None
+                            st["row_frames"] += frames[b]
+                            slot[b] = None
+                    free = [b for b, r in enumerate(slot) if r is None]
+                    take = [i for i in queue if lens[i] <= kv_len and kv_len + int(rows[i].max_new_tokens) <= self.max_seq][:len(free)]
+                    if take:
+                        e, npd, tr, tab = group(take)
+                        self.stream_admit(free[:len(take)], e, npd, tr, tab)
+                        for b, r in zip(free, take):
+                            slot[b] = r
+                        queue = [i for i in queue if i not in take]
+                s1 = self.stats()
+                st["admit_calls"] += s1["admit_calls"]
+                st["admitted_rows"] += s1["admitted_rows"]
+            finally:
+                st["frames_run"] += self.stream_close()
+        st["graph_captures"] = self.stats()["graph_captures"] - caps0
+        st["occupancy"] = st["row_frames"] / max(1, st["frames_run"] * mb)
+        self.last_refill = st
+        F = max([1] + [int(x.shape[0]) for x in out_codes])
+        codes_all = torch.zeros(N, F, G, dtype=torch.int64, device=dev)
+        codes_all[:, :, 0] = eos
+        hidden_all = torch.zeros(N, F, H, dtype=torch.float32, device=dev) if output_hidden_states else None
+        tokens = torch.full((N, F + 1), eos, dtype=torch.int64, device=dev)
+        for i in range(N):
+            n = int(out_codes[i].shape[0])
+            codes_all[i, :n] = out_codes[i]
+            tokens[i, :n] = out_codes[i][:, 0]
+            if hidden_all is not None:
+                hidden_all[i, :n] = out_hidden[i]
+        return TalkerGenerateOutput(codes=codes_all, hidden=hidden_all, tokens=tokens, n_frames=F)
 
     @_lib.locked
     def debug_logits(self) -> torch.Tensor:
