@@ -51,7 +51,8 @@ const char* qtts_last_error(void);
  * engine takes head_dim 64 | 128 and GQA groups of 1..8; 14: + qtts_row_sampling, qtts_talker_generate_rows,
  * qtts_talker_stream_begin_rows, qtts_talker_stats.graph_captures / row_table_last (appended); 15: + qtts_talker_stream_begin_admitting,
  * qtts_talker_stream_admit, qtts_talker_stream_rows, qtts_talker_stats.admit_calls / admitted_rows (two words IN FRONT of row_table_last:
- * the struct's tail moved by 8 bytes)). */
+ * the struct's tail moved by 8 bytes); still 15: + qtts_codec_stream_reset_rows, qtts_codec_stream_push_rows -- two entry points
+ * added, no signature and no struct layout changed; a binding that needs them finds out by looking the symbols up). */
 #define QTTS_ABI_VERSION 15
 int qtts_abi_version(void);
 
@@ -148,6 +149,21 @@ int qtts_codec_get_stats(qtts_codec* c, qtts_codec_stats* out);
 
 int qtts_codec_stream_begin(qtts_codec* c, int32_t batch);
 int qtts_codec_stream_push(qtts_codec* c, const int64_t* codes_dev, int32_t n_frames, float* wav_dev, void* stream);
+/* Per-slot form of the streaming decode.  After qtts_codec_stream_begin(c, B) the handle owns B SLOTS (rows 0..B-1), each with its own
+ * conv / KV carries and its own position; qtts_codec_stream_push is the push of all B slots in order.
+ *   reset_rows: a new sequence starts in each listed slot -- its carries are zeroed by a kernel on `stream` (ordered with the pushes
+ *     before and after it on that stream; no hipMemset, no null stream, no device-wide synchronisation -- the small
+ *     host-to-device copy of the ids may still hold the host until the stream has taken it), its position returns to 0.  The other slots are untouched.
+ *   push_rows: the next n_frames frames of the n_rows listed slots, in the order listed: codes_dev int64 (n_rows, num_quantizers,
+ *     n_frames) -> wav_dev float (n_rows, n_frames * total_upsample).  Slots not listed do not advance.  Each listed slot continues at
+ *     its own position (RoPE, attention-window padding), so slots admitted at different times decode side by side and every slot's
+ *     concatenated packets equal `forward` on its whole sequence.
+ * Refusals, all raised before anything is launched (a refused call changes no slot): QTTS_ERR_STATE before stream_begin;
+ * QTTS_ERR_ARG for n_rows < 1, a row id outside [0, B) or listed twice (the message names the id); QTTS_ERR_LIMIT when the packet plus
+ * the carried rows of n_rows sequences exceed the workspace (the rule of stream_push with n_rows in place of B). */
+int qtts_codec_stream_reset_rows(qtts_codec* c, int32_t n_rows, const int32_t* row_ids_host, void* stream);
+int qtts_codec_stream_push_rows(qtts_codec* c, int32_t n_rows, const int32_t* row_ids_host, const int64_t* codes_dev, int32_t n_frames,
+                                float* wav_dev, void* stream);
 
 /* Test/diagnostic hook: run Qwen3TTSTokenizerV2Decoder.forward on codes_dev (B, Q, T) up to and including
  * `stage` and copy that stage's activation, channel-last float (B, L, C), to out_dev (capacity `cap` floats).

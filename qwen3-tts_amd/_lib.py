@@ -99,7 +99,7 @@ ABI_VERSION = 15          # include/qtts.h; bumped on any signature change
 # every symbol include/qtts.h declares (checked by tests/test_host_logic.py::test_abi_exports_every_declared_symbol without a GPU)
 SYMBOLS = ["qtts_last_error", "qtts_abi_version", "qtts_set_option", "qtts_get_option", "qtts_codec_create", "qtts_codec_destroy", "qtts_codec_bind",
            "qtts_codec_finalize", "qtts_codec_forward", "qtts_codec_decode", "qtts_codec_forward_stage",
-           "qtts_codec_stream_begin", "qtts_codec_stream_push", "qtts_codec_get_stats",
+           "qtts_codec_stream_begin", "qtts_codec_stream_push", "qtts_codec_stream_reset_rows", "qtts_codec_stream_push_rows", "qtts_codec_get_stats",
            "qtts_encoder_create", "qtts_encoder_destroy", "qtts_encoder_bind", "qtts_encoder_finalize", "qtts_encoder_frames",
            "qtts_encoder_encode",
            "qtts_speaker_create", "qtts_speaker_destroy", "qtts_speaker_bind", "qtts_speaker_finalize", "qtts_speaker_mel_frames",
@@ -150,6 +150,9 @@ def load_library():
     if not os.path.exists(path):
         raise QttsError(-100, f"{path} not found -- run `python qwen3-tts_amd/build.py` (or __graft_entry__.build())")
     lib = C.CDLL(path)
+    missing = [s for s in SYMBOLS if not hasattr(lib, s)]
+    if missing:          # (entry points added without a version bump: a stale build shows here)
+        raise QttsError(-101, f"{path} does not export {', '.join(missing)}; rebuild")
     vp, i32, i64p, f32p = C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.c_void_p
     lib.qtts_last_error.restype = C.c_char_p
     lib.qtts_abi_version.restype = C.c_int
@@ -166,6 +169,8 @@ def load_library():
     lib.qtts_codec_get_stats.argtypes = [vp, C.POINTER(CodecStatsC)]
     lib.qtts_codec_stream_begin.argtypes = [vp, i32]
     lib.qtts_codec_stream_push.argtypes = [vp, vp, i32, f32p, vp]
+    lib.qtts_codec_stream_reset_rows.argtypes = [vp, i32, C.POINTER(C.c_int32), vp]
+    lib.qtts_codec_stream_push_rows.argtypes = [vp, i32, C.POINTER(C.c_int32), vp, i32, f32p, vp]
     lib.qtts_encoder_create.argtypes = [C.POINTER(EncoderConfigC), C.POINTER(vp)]
     lib.qtts_encoder_destroy.argtypes = [vp]
     lib.qtts_encoder_destroy.restype = None

@@ -175,6 +175,37 @@ class CodecDecoderEngine:
                                                         C.c_void_p(wav.data_ptr()), self._stream()))
         return wav.unsqueeze(1)
 
+    @_lib.locked
+    def stream_reset_rows(self, row_ids: List[int]):
+        """A new sequence starts in each listed slot of the session `stream_begin(batch)` opened (include/qtts.h
+        `qtts_codec_stream_reset_rows`): its carries are zeroed on the current stream, its position returns to 0; the other slots run on."""
+        if len(row_ids) < 1:
+            raise ValueError("stream_reset_rows: no row ids given")
+        ids = (C.c_int32 * len(row_ids))(*[int(r) for r in row_ids])
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.qtts_codec_stream_reset_rows(self._h, len(row_ids), ids, self._stream()))
+
+    @_lib.locked
+    def stream_push_rows(self, row_ids: List[int], codes: torch.Tensor) -> torch.Tensor:
+        """Decode the next packet of the listed slots only (include/qtts.h `qtts_codec_stream_push_rows`): codes (len(row_ids), Q, k)
+        int64, row m for slot row_ids[m] -> (len(row_ids), 1, k * total_upsample).  Every slot continues at its own position, so slots
+        that were reset at different times decode side by side; a slot's concatenated packets equal `forward` on its whole sequence."""
+        self._check_codes(codes, 1)
+        M, _, k = codes.shape
+        if M != len(row_ids):
+            raise ValueError(f"stream_push_rows: {len(row_ids)} row ids for {M} rows of codes")
+        if M < 1 or k < 1:
+            raise ValueError(f"stream_push_rows: an empty packet ({M} rows, {k} frames)")
+        if int(codes.min()) < 0 or int(codes.max()) >= self.config.codebook_size:
+            raise ValueError("stream_push_rows: code index out of range")
+        codes = codes.to(self.device, torch.long).contiguous()
+        ids = (C.c_int32 * max(1, M))(*[int(r) for r in row_ids])
+        wav = torch.empty(M, k * self.config.total_upsample, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.qtts_codec_stream_push_rows(self._h, M, ids, C.c_void_p(codes.data_ptr()), int(k),
+                                                             C.c_void_p(wav.data_ptr()), self._stream()))
+        return wav.unsqueeze(1)
+
     def stream(self, left_context_size: int = 25) -> "CodecStreamDecoder":
         """A packet-by-packet decoder bound to this engine (see CodecStreamDecoder)."""
         return CodecStreamDecoder(self.forward, self.config.total_upsample, left_context_size)

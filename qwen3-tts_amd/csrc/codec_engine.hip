@@ -171,14 +171,23 @@ struct qtts_codec {
         }
     }
 
-    // ---- streaming (state-carrying) decode: one session per handle, B sequences advancing in lockstep
+    // ---- streaming (state-carrying) decode: one session per handle, B slots, each with its own carries and its own position
     struct Carry { DevBuf d; int h = 0, C = 0; };
-    std::vector<Carry> carry;           // in the order the stateful layers run
-    DevBuf stream_npad;                 // [B] left-pad count of the staged KV window
-    std::vector<int> stream_npad_host;
+    std::vector<Carry> carry;           // in the order the stateful layers run; each holds [B slots][h][C]
     int stream_B = 0;                   // 0 = no session
-    int64_t stream_t = 0;               // frames decoded so far
+    std::vector<int64_t> slot_t;        // [B] frames decoded so far, per slot
+    DevBuf stream_meta;                 // the rows of one push: [M] slot map | [M] first position | [M] left-pad count of the KV window
+    // Pageable host memory, rewritten by the next call: right only because the runtime has consumed a pageable source (staged it, or
+    // waited for the copy) when hipMemcpyAsync returns -- so a push or reset may block the host on the stream for that copy.  A
+    // hipGraph of the push needs pinned memory here.  (stream_reset_host alike.)
+    std::vector<int> stream_meta_host;
+    DevBuf stream_reset_ids;            // [<= B] the slots of one reset
+    std::vector<int> stream_reset_host;
     void stream_begin(int B);
+    void stream_check_rows(int n_rows, const int* ids, const char* who) const;
+    void stream_reset_rows(int n_rows, const int* ids, hipStream_t st);
+    void stream_push_rows(int n_rows, const int* ids, const int64_t* codes, int n, float* wav, hipStream_t st);
+    void stream_run(int M, const int64_t* codes, int n, float* wav, hipStream_t st, bool dry);
     void stream_push(const int64_t* codes, int n, float* wav, hipStream_t st);
 
     std::vector<float>& P(const std::string& n) {
@@ -716,6 +725,9 @@ void qtts_codec::forward(const int64_t* codes, int B, int64_t sb, int64_t sq, in
 // per transformer layer): algorithm and its equality with the whole-sequence forward in oracle/codec_stream_ref.py.
 // Every stateful layer is run by the UNCHANGED kernels of forward() on a staged buffer [carried rows | new rows]; the
 // outputs of the carried rows are discarded by the next staging step (`skip`).
+// The handle owns B SLOTS after stream_begin(B): carries and position per slot, so that a push may decode any subset of them
+// (dense [M][..] activations, the carries addressed through a device slot map) and a slot may be reset for a new sequence while the
+// others run on.  stream_push() is the push of all slots in order.
 void qtts_codec::stream_begin(int B) {
     QTTS_REQUIRE(finalized, QTTS_ERR_STATE, "codec: finalize() first");
     QTTS_REQUIRE(B >= 1 && B <= cfg.max_batch, QTTS_ERR_LIMIT, "codec stream: batch exceeds max_batch");
@@ -739,20 +751,78 @@ void qtts_codec::stream_begin(int B) {
         carry[i].d.ensure(std::max<size_t>(bytes, 16));
         QTTS_CHECK_HIP(hipMemset(carry[i].d.p, 0, std::max<size_t>(bytes, 16)));   // zeros == the causal left padding
     }
-    // hipMemset runs on the null stream and may return before it has executed; stream_push() launches on the caller's
+    // hipMemset runs on the null stream and may return before it has executed; the pushes launch on the caller's
     // stream, which does not order against the null stream when it is a non-blocking one (PyTorch's pool streams are).
     QTTS_CHECK_HIP(hipDeviceSynchronize());
-    stream_npad.ensure((size_t)B * sizeof(int));
-    stream_npad_host.assign(B, 0);
+    QTTS_REQUIRE((int)carry.size() <= StreamCarryTable::MAX, QTTS_ERR_LIMIT, "codec stream: more stateful layers than the reset table holds");
+    stream_meta.ensure((size_t)3 * B * sizeof(int));
+    stream_meta_host.assign((size_t)3 * B, 0);
+    stream_reset_ids.ensure((size_t)B * sizeof(int));
+    stream_reset_host.assign(B, 0);
     stream_B = B;
-    stream_t = 0;
+    slot_t.assign(B, 0);
 }
 
-void qtts_codec::stream_push(const int64_t* codes, int n, float* wav, hipStream_t st) {
-    const auto& c = cfg;
+// ids: n_rows distinct slots of the session.  Checked before anything is launched: a refused call changes no slot.
+void qtts_codec::stream_check_rows(int n_rows, const int* ids, const char* who) const {
     QTTS_REQUIRE(stream_B > 0, QTTS_ERR_STATE, "codec stream: stream_begin() first");
+    QTTS_REQUIRE(n_rows >= 1 && ids, QTTS_ERR_ARG, std::string(who) + ": n_rows >= 1");
+    std::vector<char> seen(stream_B, 0);
+    for (int m = 0; m < n_rows; ++m) {
+        const int id = ids[m];
+        QTTS_REQUIRE(id >= 0 && id < stream_B, QTTS_ERR_ARG,
+                     std::string(who) + ": row " + std::to_string(id) + " is not a row of this stream (" + std::to_string(stream_B) + " rows)");
+        QTTS_REQUIRE(!seen[id], QTTS_ERR_ARG, std::string(who) + ": row " + std::to_string(id) + ": listed twice");
+        seen[id] = 1;
+    }
+}
+
+// A sequence starts in each listed slot: its carries are zeroed on `st` (ordered with the pushes before and after it on that
+// stream), its position returns to 0.
+void qtts_codec::stream_reset_rows(int n_rows, const int* ids, hipStream_t st) {
+    stream_check_rows(n_rows, ids, "stream_reset_rows");
+    StreamCarryTable tab{};
+    tab.n = (int)carry.size();
+    for (int k = 0; k < tab.n; ++k) { tab.state[k] = carry[k].d.as<float>(); tab.elems4[k] = carry[k].h * carry[k].C / 4; }
+    for (int m = 0; m < n_rows; ++m) stream_reset_host[m] = ids[m];
+    QTTS_CHECK_HIP(hipMemcpyAsync(stream_reset_ids.p, stream_reset_host.data(), (size_t)n_rows * sizeof(int), hipMemcpyHostToDevice, st));
+    launch_stream_reset_slots(tab, stream_reset_ids.as<int>(), n_rows, st);
+    for (int m = 0; m < n_rows; ++m) slot_t[ids[m]] = 0;
+}
+
+// the lockstep push: every slot, in order
+void qtts_codec::stream_push(const int64_t* codes, int n, float* wav, hipStream_t st) {
+    QTTS_REQUIRE(stream_B > 0, QTTS_ERR_STATE, "codec stream: stream_begin() first");
+    std::vector<int> ids(stream_B);
+    for (int b = 0; b < stream_B; ++b) ids[b] = b;
+    stream_push_rows(stream_B, ids.data(), codes, n, wav, st);
+}
+
+// A packet of n new frames for the M listed slots.  The positions go up with the slot map in one copy; n and M are the only host
+// scalars in the launch arguments.
+void qtts_codec::stream_push_rows(int M, const int* ids, const int64_t* codes, int n, float* wav, hipStream_t st) {
+    stream_check_rows(M, ids, "stream_push_rows");
     QTTS_REQUIRE(n >= 1 && codes && wav, QTTS_ERR_ARG, "codec stream: empty packet");
-    const int B = stream_B;
+    stream_run(M, codes, n, wav, st, true);            // the workspace rule, before a carry is touched
+    const int W1 = cfg.sliding_window - 1;
+    int* meta = stream_meta_host.data();
+    for (int m = 0; m < M; ++m) {
+        const int64_t t = slot_t[ids[m]];
+        meta[m] = ids[m];
+        meta[M + m] = (int)t;
+        meta[2 * M + m] = W1 - (int)std::min<int64_t>(t, W1);               // carried KV rows that do not exist yet
+    }
+    QTTS_CHECK_HIP(hipMemcpyAsync(stream_meta.p, meta, (size_t)3 * M * sizeof(int), hipMemcpyHostToDevice, st));
+    stream_run(M, codes, n, wav, st, false);
+    for (int m = 0; m < M; ++m) slot_t[ids[m]] += n;
+}
+
+// The one orchestration of a push.  dry: walk the shapes and apply the workspace rule only, launch nothing.
+void qtts_codec::stream_run(int B, const int64_t* codes, int n, float* wav, hipStream_t st, bool dry) {
+    const auto& c = cfg;
+    const int* slot = stream_meta.as<int>();
+    const int* pos0 = slot + B;
+    const int* npad = slot + 2 * B;
     float* pool[4] = {buf[0].as<float>(), buf[1].as<float>(), buf[2].as<float>(), buf[3].as<float>()};
     auto fits = [&](int64_t rows, int C) {
         QTTS_REQUIRE((size_t)rows * (size_t)C <= buf_elems, QTTS_ERR_LIMIT,
@@ -766,7 +836,11 @@ void qtts_codec::stream_push(const int64_t* codes, int n, float* wav, hipStream_
         }
         throw Error(QTTS_ERR_STATE, "codec stream: out of workspace buffers");
     };
-    size_t ci = 0;                                   // next carry slot
+    auto G = [&](const Lin& l, const float* A, int lda, int Mr, int Tr, float* Cc, int ldc, int act = ACT_NONE, const float* res = nullptr,
+                 int ldr = 0, const float* scale = nullptr, const Snake* sn = nullptr) {
+        if (!dry) gemm(l, A, lda, Mr, Tr, Cc, ldc, act, res, ldr, scale, sn, st);
+    };
+    size_t ci = 0;                                   // next carry
     // x: current activation, T rows per sequence of which the first `skip` are to be ignored, C channels
     float* x = nullptr; int T = n, skip = 0, C = 0;
     auto stage = [&](float* dst) {                   // dst = [carry | valid rows of x]; refresh the carry; x <- dst
@@ -774,13 +848,15 @@ void qtts_codec::stream_push(const int64_t* codes, int n, float* wav, hipStream_
         QTTS_REQUIRE(k.C == C, QTTS_ERR_STATE, "codec stream: carry/channel mismatch");
         const int nv = T - skip;
         fits((int64_t)B * (k.h + nv), C);
-        launch_stage_rows(x, T, skip, nv, k.d.as<float>(), k.h, dst, B, C, st);
-        launch_save_tail(dst, k.h + nv, k.d.as<float>(), k.h, B, C, st);
+        if (!dry) {
+            launch_stage_rows_slots(x, T, skip, nv, k.d.as<float>(), slot, k.h, dst, B, C, st);
+            launch_save_tail_slots(dst, k.h + nv, k.d.as<float>(), slot, k.h, B, C, st);
+        }
         x = dst; T = k.h + nv; skip = k.h;
     };
     auto compact = [&](float* dst) {                 // drop the ignored rows
         const int nv = T - skip;
-        launch_stage_rows(x, T, skip, nv, nullptr, 0, dst, B, C, st);
+        if (!dry) launch_stage_rows(x, T, skip, nv, nullptr, 0, dst, B, C, st);
         x = dst; T = nv; skip = 0;
     };
 
@@ -788,15 +864,15 @@ void qtts_codec::stream_push(const int64_t* codes, int n, float* wav, hipStream_
     float* g = pool[1];
     x = pool[0]; C = c.codebook_dim;
     fits((int64_t)B * n, std::max(2 * vq, C));
-    launch_rvq_gather(codes, B, c.num_quantizers, n, (int64_t)c.num_quantizers * n, n, 1, 0, n, tables.as<float>(),
-                      c.codebook_size, vq, g, err_flag.as<int>(), st);
-    gemm(rvq_out, g, 2 * vq, B * n, n, x, C, ACT_NONE, nullptr, 0, nullptr, nullptr, st);
+    if (!dry) launch_rvq_gather(codes, B, c.num_quantizers, n, (int64_t)c.num_quantizers * n, n, 1, 0, n, tables.as<float>(),
+                                c.codebook_size, vq, g, err_flag.as<int>(), st);
+    G(rvq_out, g, 2 * vq, B * n, n, x, C);
     // ---- pre_conv k=3
     {
         float* s = other({x}); stage(s);
         float* y = other({x});
         fits((int64_t)B * T, c.latent_dim);
-        gemm(pre_conv, x, C, B * T, T, y, c.latent_dim, ACT_NONE, nullptr, 0, nullptr, nullptr, st);
+        G(pre_conv, x, C, B * T, T, y, c.latent_dim);
         x = y; C = c.latent_dim;
         compact(other({x}));
     }
@@ -805,37 +881,34 @@ void qtts_codec::stream_push(const int64_t* codes, int n, float* wav, hipStream_
         const int H = c.hidden_size, I = c.intermediate_size, W1 = c.sliding_window - 1;
         const int qd = c.num_attention_heads * c.head_dim, kvd = c.num_key_value_heads * c.head_dim, qw = qd + 2 * kvd;
         const int M = B * n;
-        const int pad = W1 - (int)std::min<int64_t>(stream_t, W1);          // carried rows that do not exist yet
-        for (int b = 0; b < B; ++b) stream_npad_host[b] = pad;
-        QTTS_CHECK_HIP(hipMemcpyAsync(stream_npad.p, stream_npad_host.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice, st));
         float* h = other({x});
         fits((int64_t)B * (W1 + n), std::max({qw, H, I}));
-        gemm(in_proj, x, C, M, n, h, H, ACT_NONE, nullptr, 0, nullptr, nullptr, st);
+        G(in_proj, x, C, M, n, h, H);
         float* a = other({h});
         float* b2 = other({h, a});
         for (auto& Ly : tl) {
-            launch_rmsnorm(h, H, Ly.n1.as<float>(), c.rms_norm_eps, a, H, M, H, st);
-            gemm(Ly.qkv, a, H, M, n, b2, qw, ACT_NONE, nullptr, 0, nullptr, nullptr, st);
-            launch_rope_offset(b2, qw, M, n, (int)stream_t, c.num_attention_heads + c.num_key_value_heads, c.head_dim,
-                               inv_freq.as<float>(), st);
-            // a <- [carried roped q|k|v rows | new rows]
             Carry& k = carry[ci++];
             QTTS_REQUIRE(k.C == qw && k.h == W1, QTTS_ERR_STATE, "codec stream: KV carry mismatch");
-            launch_stage_rows(b2, n, 0, n, k.d.as<float>(), W1, a, B, qw, st);
-            launch_save_tail(a, W1 + n, k.d.as<float>(), W1, B, qw, st);
+            if (dry) continue;
+            launch_rmsnorm(h, H, Ly.n1.as<float>(), c.rms_norm_eps, a, H, M, H, st);
+            G(Ly.qkv, a, H, M, n, b2, qw);
+            launch_rope_offset_rows(b2, qw, M, n, pos0, c.num_attention_heads + c.num_key_value_heads, c.head_dim, inv_freq.as<float>(), st);
+            // a <- [carried roped q|k|v rows | new rows]
+            launch_stage_rows_slots(b2, n, 0, n, k.d.as<float>(), slot, W1, a, B, qw, st);
+            launch_save_tail_slots(a, W1 + n, k.d.as<float>(), slot, W1, B, qw, st);
             AttnRowsParams ap{};
             ap.qkv = a; ap.ld = qw; ap.q_off = 0; ap.k_off = qd; ap.v_off = qd + kvd;
             ap.B = B; ap.T = W1 + n; ap.nh = c.num_attention_heads; ap.nkv = c.num_key_value_heads; ap.hd = c.head_dim;
-            ap.window = c.sliding_window; ap.n_pad = stream_npad.as<int>(); ap.out = b2; ap.ldo = qd;
+            ap.window = c.sliding_window; ap.n_pad = npad; ap.out = b2; ap.ldo = qd;
             launch_attn_rows(ap, st);                                       // b2: [B][W1+n][qd], rows >= W1 are the new ones
             launch_stage_rows(b2, W1 + n, W1, n, nullptr, 0, a, B, qd, st);  // a: compact [B*n][qd]
-            gemm(Ly.o, a, qd, M, n, h, H, ACT_NONE, h, H, Ly.ls1.as<float>(), nullptr, st);
+            G(Ly.o, a, qd, M, n, h, H, ACT_NONE, h, H, Ly.ls1.as<float>());
             launch_rmsnorm(h, H, Ly.n2.as<float>(), c.rms_norm_eps, a, H, M, H, st);
-            gemm(Ly.gu, a, H, M, n, b2, I, ACT_SWIGLU, nullptr, 0, nullptr, nullptr, st);
-            gemm(Ly.down, b2, I, M, n, h, H, ACT_NONE, h, H, Ly.ls2.as<float>(), nullptr, st);
+            G(Ly.gu, a, H, M, n, b2, I, ACT_SWIGLU);
+            G(Ly.down, b2, I, M, n, h, H, ACT_NONE, h, H, Ly.ls2.as<float>());
         }
-        launch_rmsnorm(h, H, t_norm.as<float>(), c.rms_norm_eps, a, H, M, H, st);
-        gemm(out_proj, a, H, M, n, b2, c.latent_dim, ACT_NONE, nullptr, 0, nullptr, nullptr, st);
+        if (!dry) launch_rmsnorm(h, H, t_norm.as<float>(), c.rms_norm_eps, a, H, M, H, st);
+        G(out_proj, a, H, M, n, b2, c.latent_dim);
         x = b2; T = n; skip = 0; C = c.latent_dim;
     }
     // ---- upsample: ConvTranspose(k = s = f, column-local) + ConvNeXt (dwconv k=7 carries 6 rows)
@@ -843,23 +916,23 @@ void qtts_codec::stream_push(const int64_t* codes, int n, float* wav, hipStream_
         const int f = c.upsampling_ratios[u];
         float* y = other({x});
         fits((int64_t)B * T * f, 4 * C);
-        gemm(ups[u].tconv, x, C, B * T, T, y, f * C, ACT_NONE, nullptr, 0, nullptr, nullptr, st);
+        G(ups[u].tconv, x, C, B * T, T, y, f * C);
         x = y; T *= f; skip *= f;
         float* s = other({x}); stage(s);                                   // x = staged y (also the residual)
         float* d = other({x});
         float* e = other({x, d});
         fits((int64_t)B * T, 4 * C);
-        launch_dwconv_ln(x, ups[u].dw_w.as<float>(), ups[u].dw_b.as<float>(), ups[u].ln_w.as<float>(),
-                         ups[u].ln_b.as<float>(), 1e-6f, d, B * T, T, C, st);
-        gemm(ups[u].pw1, d, C, B * T, T, e, 4 * C, ACT_GELU, nullptr, 0, nullptr, nullptr, st);
-        gemm(ups[u].pw2, e, 4 * C, B * T, T, x, C, ACT_NONE, x, C, ups[u].gamma.as<float>(), nullptr, st);
+        if (!dry) launch_dwconv_ln(x, ups[u].dw_w.as<float>(), ups[u].dw_b.as<float>(), ups[u].ln_w.as<float>(),
+                                   ups[u].ln_b.as<float>(), 1e-6f, d, B * T, T, C, st);
+        G(ups[u].pw1, d, C, B * T, T, e, 4 * C, ACT_GELU);
+        G(ups[u].pw2, e, 4 * C, B * T, T, x, C, ACT_NONE, x, C, ups[u].gamma.as<float>());
     }
     // ---- decoder.0 conv k=7
     {
         float* s = other({x}); stage(s);
         float* y = other({x});
         fits((int64_t)B * T, c.decoder_dim);
-        gemm(dec0, x, C, B * T, T, y, c.decoder_dim, ACT_NONE, nullptr, 0, nullptr, nullptr, st);
+        G(dec0, x, C, B * T, T, y, c.decoder_dim);
         x = y; C = c.decoder_dim;
     }
     // ---- decoder blocks
@@ -868,10 +941,10 @@ void qtts_codec::stream_push(const int64_t* codes, int n, float* wav, hipStream_
         {   // SnakeBeta (elementwise) + ConvTranspose(2r, r): output block t mixes input rows t and t-1
             float* s = other({x}); stage(s);                               // carry = 1 pre-activation row
             float* a = other({x});
-            launch_snake(x, bk.act.ea.as<float>(), bk.act.ib.as<float>(), a, (int64_t)B * T, C, st);
+            if (!dry) launch_snake(x, bk.act.ea.as<float>(), bk.act.ib.as<float>(), a, (int64_t)B * T, C, st);
             float* b = other({x, a});
             fits((int64_t)B * T * bk.r, bk.cout);
-            gemm(bk.tconv, a, C, B * T, T, b, bk.r * bk.cout, ACT_NONE, nullptr, 0, nullptr, nullptr, st);
+            G(bk.tconv, a, C, B * T, T, b, bk.r * bk.cout);
             x = b; T *= bk.r; skip *= bk.r; C = bk.cout;
         }
         for (int j = 0; j < 3; ++j) {
@@ -879,9 +952,9 @@ void qtts_codec::stream_push(const int64_t* codes, int n, float* wav, hipStream_
             float* s = other({x}); stage(s);                               // x = [carried unit inputs | new], also the residual
             float* sA = other({x});
             float* sB = other({x, sA});
-            launch_snake(x, un.a1.ea.as<float>(), un.a1.ib.as<float>(), sA, (int64_t)B * T, C, st);
-            gemm(un.c1, sA, C, B * T, T, sB, C, ACT_SNAKE, nullptr, 0, nullptr, &un.a2, st);
-            gemm(un.c2, sB, C, B * T, T, sA, C, ACT_NONE, x, C, nullptr, nullptr, st);
+            if (!dry) launch_snake(x, un.a1.ea.as<float>(), un.a1.ib.as<float>(), sA, (int64_t)B * T, C, st);
+            G(un.c1, sA, C, B * T, T, sB, C, ACT_SNAKE, nullptr, 0, nullptr, &un.a2);
+            G(un.c2, sB, C, B * T, T, sA, C, ACT_NONE, x, C);
             x = sA;
         }
     }
@@ -889,12 +962,13 @@ void qtts_codec::stream_push(const int64_t* codes, int n, float* wav, hipStream_
     {
         float* s = other({x}); stage(s);
         float* a = other({x});
-        launch_snake(x, final_act.ea.as<float>(), final_act.ib.as<float>(), a, (int64_t)B * T, C, st);
         QTTS_REQUIRE(C == final_c, QTTS_ERR_ARG, "final conv channel mismatch");
-        launch_final_conv(a, final_w.as<float>(), final_b, wav, nullptr, (int64_t)B * T, T, C, (int64_t)n * up_total, skip, st);
+        if (!dry) {
+            launch_snake(x, final_act.ea.as<float>(), final_act.ib.as<float>(), a, (int64_t)B * T, C, st);
+            launch_final_conv(a, final_w.as<float>(), final_b, wav, nullptr, (int64_t)B * T, T, C, (int64_t)n * up_total, skip, st);
+        }
     }
     QTTS_REQUIRE(ci == carry.size(), QTTS_ERR_STATE, "codec stream: carry bookkeeping out of step");
-    stream_t += n;
 }
 
 // ============================================================================================ C ABI
@@ -1121,6 +1195,20 @@ int qtts_codec_stream_push(qtts_codec* c, const int64_t* codes_dev, int32_t n_fr
     QTTS_REQUIRE(c && codes_dev && wav_dev, QTTS_ERR_ARG, "null argument");
     c->stream_push(codes_dev, n_frames, wav_dev, (hipStream_t)stream);
     c->check_codes_flag((hipStream_t)stream);      // a bad code must fail THIS call (and not poison the next one through a stale flag)
+    QTTS_API_END
+}
+int qtts_codec_stream_reset_rows(qtts_codec* c, int32_t n_rows, const int32_t* row_ids_host, void* stream) {
+    QTTS_API_BEGIN
+    QTTS_REQUIRE(c, QTTS_ERR_ARG, "null handle");
+    c->stream_reset_rows(n_rows, row_ids_host, (hipStream_t)stream);
+    QTTS_API_END
+}
+int qtts_codec_stream_push_rows(qtts_codec* c, int32_t n_rows, const int32_t* row_ids_host, const int64_t* codes_dev, int32_t n_frames,
+                                float* wav_dev, void* stream) {
+    QTTS_API_BEGIN
+    QTTS_REQUIRE(c, QTTS_ERR_ARG, "null handle");
+    c->stream_push_rows(n_rows, row_ids_host, codes_dev, n_frames, wav_dev, (hipStream_t)stream);
+    c->check_codes_flag((hipStream_t)stream);
     QTTS_API_END
 }
 

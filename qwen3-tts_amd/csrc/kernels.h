@@ -135,11 +135,23 @@ void launch_rope_inplace(float* qkv, int ld, int rows, int T, int n_heads_total 
 // src has src_T rows per sequence, dst h + n.  state may be null when h == 0 (plain compaction).
 void launch_stage_rows(const float* src, int src_T, int skip, int n, const float* state, int h, float* dst, int B, int C,
                        hipStream_t st);
-// state[b] = the last h rows of buf[b] (Tp rows per sequence)
-void launch_save_tail(const float* buf, int Tp, float* state, int h, int B, int C, hipStream_t st);
-// launch_rope_inplace with positions pos0 + (row % T)
-void launch_rope_offset(float* qkv, int ld, int rows, int T, int pos0, int n_heads_total, int hd, const float* inv_freq,
-                        hipStream_t st);
+// per-slot carries: the same staging with row m of the push on carry slot[m] (device map), `state + slot[m] * h * C`
+void launch_stage_rows_slots(const float* src, int src_T, int skip, int n, const float* state, const int* slot, int h, float* dst,
+                             int M, int C, hipStream_t st);
+// state[slot[m]] = the last h rows of buf[m] (Tp rows per sequence)
+void launch_save_tail_slots(const float* buf, int Tp, float* state, const int* slot, int h, int M, int C, hipStream_t st);
+// launch_rope_inplace with positions pos0[row / T] + (row % T), pos0 a device array with one entry per sequence
+void launch_rope_offset_rows(float* qkv, int ld, int rows, int T, const int* pos0, int n_heads_total, int hd, const float* inv_freq,
+                             hipStream_t st);
+// every carry of a stream, passed by value to the reset kernel: state[k] holds elems4[k] float4 per slot
+struct StreamCarryTable {
+    static constexpr int MAX = 64;
+    float* state[MAX];
+    int elems4[MAX];
+    int n;
+};
+// zero all carries of the n_slots slots listed in the device array `slot`
+void launch_stream_reset_slots(const StreamCarryTable& t, const int* slot, int n_slots, hipStream_t st);
 
 // ---- codec ENCODER helpers (Mimi encode) -- encoder_kernels.hip
 void launch_elu(const float* x, float* y, int64_t n, hipStream_t st);

@@ -1,4 +1,4 @@
-// stream_kernels.hip -- the three small kernels the state-carrying codec decode adds: everything else in
+// stream_kernels.hip -- the small kernels the state-carrying codec decode adds: everything else in
 // that path reuses the validated kernels of the non-streaming decoder.  Thread-independent code (no LDS, no cross-lane
 // ops): tests/hostemu also executes THESE SOURCES on the CPU through a sequential block/thread interpreter.
 #include "common.h"
@@ -10,6 +10,7 @@ namespace qtts {
 // Every layer of the decoder is causal, so a packet of new frames only needs, per stateful layer, the last
 // (k-1)*dilation input rows of the previous packet (oracle/codec_stream_ref.py).  `stage_rows` builds
 // [carried rows | new rows] so that the UNCHANGED conv / attention kernels run on it; `save_tail` refreshes the carry.
+// `stage_rows` itself is the form without a carry (h == 0 in the stream: plain compaction); the carried forms are below.
 __global__ __launch_bounds__(256) void stage_rows_kernel(const float* src, int src_T, int skip, int n, const float* state,
                                                          int h, float* dst, int C4) {
     const int r = blockIdx.x, b = blockIdx.y;
@@ -26,28 +27,48 @@ void launch_stage_rows(const float* src, int src_T, int skip, int n, const float
     QTTS_CHECK_HIP(hipGetLastError());
 }
 
-__global__ __launch_bounds__(256) void save_tail_kernel(const float* buf, int Tp, float* state, int h, int C4) {
-    const int j = blockIdx.x, b = blockIdx.y;
-    const float4* from = reinterpret_cast<const float4*>(buf) + ((size_t)b * Tp + (Tp - h + j)) * C4;
-    float4* to = reinterpret_cast<float4*>(state) + ((size_t)b * h + j) * C4;
+// ---------------------------------------------------------------------------------- per-slot carries
+// A stream owns B slots, each with its own carries and its own position; a push decodes a packet for any M of them.  The staged and
+// activation buffers stay dense [M][h + n][C]; only the carry is addressed through the device slot map: row m of the push reads and
+// refreshes state[slot[m]].  (The lockstep push is the identity map.)
+__global__ __launch_bounds__(256) void stage_rows_slots_kernel(const float* src, int src_T, int skip, int n, const float* state,
+                                                               const int* slot, int h, float* dst, int C4) {
+    const int r = blockIdx.x, m = blockIdx.y;
+    const float4* from = r < h ? reinterpret_cast<const float4*>(state) + ((size_t)slot[m] * h + r) * C4
+                               : reinterpret_cast<const float4*>(src) + ((size_t)m * src_T + skip + (r - h)) * C4;
+    float4* to = reinterpret_cast<float4*>(dst) + ((size_t)m * (h + n) + r) * C4;
     for (int c = threadIdx.x; c < C4; c += 256) to[c] = from[c];
 }
-void launch_save_tail(const float* buf, int Tp, float* state, int h, int B, int C, hipStream_t st) {
-    if (h == 0) return;
-    QTTS_REQUIRE(C % 4 == 0 && Tp >= h, QTTS_ERR_ARG, "save_tail: bad shape");
-    hipLaunchKernelGGL(save_tail_kernel, dim3(h, B), dim3(256), 0, st, buf, Tp, state, h, C / 4);
+void launch_stage_rows_slots(const float* src, int src_T, int skip, int n, const float* state, const int* slot, int h, float* dst,
+                             int M, int C, hipStream_t st) {
+    QTTS_REQUIRE(C % 4 == 0 && n >= 1 && h >= 1 && skip >= 0 && skip + n <= src_T && M >= 1, QTTS_ERR_ARG, "stage_rows_slots: bad shape");
+    QTTS_REQUIRE(state && slot, QTTS_ERR_ARG, "stage_rows_slots: state or slot map missing");
+    hipLaunchKernelGGL(stage_rows_slots_kernel, dim3(h + n, M), dim3(256), 0, st, src, src_T, skip, n, state, slot, h, dst, C / 4);
     QTTS_CHECK_HIP(hipGetLastError());
 }
 
-// rotate-half RoPE at positions pos0 + (row % T) (a packet that starts at frame pos0 of its stream)
-__global__ __launch_bounds__(256) void rope_offset_kernel(float* qkv, int ld, int T, int pos0, int nheads, int hd,
-                                                          const float* inv_freq, int64_t total) {
+__global__ __launch_bounds__(256) void save_tail_slots_kernel(const float* buf, int Tp, float* state, const int* slot, int h, int C4) {
+    const int j = blockIdx.x, m = blockIdx.y;
+    const float4* from = reinterpret_cast<const float4*>(buf) + ((size_t)m * Tp + (Tp - h + j)) * C4;
+    float4* to = reinterpret_cast<float4*>(state) + ((size_t)slot[m] * h + j) * C4;
+    for (int c = threadIdx.x; c < C4; c += 256) to[c] = from[c];
+}
+void launch_save_tail_slots(const float* buf, int Tp, float* state, const int* slot, int h, int M, int C, hipStream_t st) {
+    QTTS_REQUIRE(C % 4 == 0 && h >= 1 && Tp >= h && M >= 1 && state && slot, QTTS_ERR_ARG, "save_tail_slots: bad shape");
+    hipLaunchKernelGGL(save_tail_slots_kernel, dim3(h, M), dim3(256), 0, st, buf, Tp, state, slot, h, C / 4);
+    QTTS_CHECK_HIP(hipGetLastError());
+}
+
+// rotate-half RoPE at positions pos0[row / T] + (row % T): T new frames per sequence, sequence m of the push starts at frame pos0[m]
+// of its own stream
+__global__ __launch_bounds__(256) void rope_offset_rows_kernel(float* qkv, int ld, int T, const int* pos0, int nheads, int hd,
+                                                               const float* inv_freq, int64_t total) {
     const int half = hd / 2;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         const int d = (int)(i % half);
         const int h = (int)((i / half) % nheads);
         const int64_t row = i / ((int64_t)half * nheads);
-        const float ang = (float)(pos0 + (int)(row % T)) * inv_freq[d];
+        const float ang = (float)(pos0[row / T] + (int)(row % T)) * inv_freq[d];
         const float c = cosf(ang), s = sinf(ang);
         float* p = qkv + row * ld + h * hd;
         const float x0 = p[d], x1 = p[d + half];
@@ -55,11 +76,26 @@ __global__ __launch_bounds__(256) void rope_offset_kernel(float* qkv, int ld, in
         p[d + half] = x1 * c + x0 * s;
     }
 }
-void launch_rope_offset(float* qkv, int ld, int rows, int T, int pos0, int n_heads_total, int hd, const float* inv_freq,
-                        hipStream_t st) {
+void launch_rope_offset_rows(float* qkv, int ld, int rows, int T, const int* pos0, int n_heads_total, int hd, const float* inv_freq,
+                             hipStream_t st) {
+    QTTS_REQUIRE(T >= 1 && rows % T == 0 && pos0, QTTS_ERR_ARG, "rope_offset_rows: bad shape");
     const int64_t total = (int64_t)rows * n_heads_total * (hd / 2);
     const int grid = (int)std::min<int64_t>((total + 255) / 256, 65535);
-    hipLaunchKernelGGL(rope_offset_kernel, dim3(grid), dim3(256), 0, st, qkv, ld, T, pos0, n_heads_total, hd, inv_freq, total);
+    hipLaunchKernelGGL(rope_offset_rows_kernel, dim3(grid), dim3(256), 0, st, qkv, ld, T, pos0, n_heads_total, hd, inv_freq, total);
+    QTTS_CHECK_HIP(hipGetLastError());
+}
+
+// zero every carry of the listed slots (zeros == the causal left padding of a sequence that starts): one launch, stream-ordered
+// with the pushes around it.  blockIdx.y = carry, blockIdx.z = listed slot.
+__global__ __launch_bounds__(256) void stream_reset_slots_kernel(StreamCarryTable t, const int* slot) {
+    const int k = blockIdx.y;
+    const int n4 = t.elems4[k];
+    float4* to = reinterpret_cast<float4*>(t.state[k]) + (size_t)slot[blockIdx.z] * n4;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n4; i += gridDim.x * 256) to[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+}
+void launch_stream_reset_slots(const StreamCarryTable& t, const int* slot, int n_slots, hipStream_t st) {
+    QTTS_REQUIRE(t.n >= 1 && t.n <= StreamCarryTable::MAX && n_slots >= 1 && slot, QTTS_ERR_ARG, "stream_reset_slots: bad shape");
+    hipLaunchKernelGGL(stream_reset_slots_kernel, dim3(16, t.n, n_slots), dim3(256), 0, st, t, slot);
     QTTS_CHECK_HIP(hipGetLastError());
 }
 

@@ -357,9 +357,16 @@ class Qwen3TTSForConditionalGeneration:
                         repetition_penalty: float = 1.05, **kwargs):
         """Streaming OUTPUT variant of `generate` (the reference returns whole utterances, qwen3_tts_model.py:513-515): a
         generator of packets; each packet is a list with, per request, the (k_i, G) codes it gained (k_i = 0 once the
-        request hit EOS, M:2283-2289).  One wave only: len(input_ids) <= max_batch.  Per-request sequences as in `generate`."""
+        request hit EOS, M:2283-2289).  One wave only: len(input_ids) <= max_batch.  Per-request sequences as in `generate`.
+
+        `schedule="refill"`: any number of requests; the talker admits queued requests into rows as they finish and the generator
+        yields its `RefillPacket` records unchanged (`TalkerEngine.generate_stream`): per row the request index, the new frames (already
+        cut at eos), and whether the request started or finished with the packet."""
         c = self.config
-        if len(input_ids) > self.talker.max_batch:
+        schedule = kwargs.get("schedule", "waves")
+        if schedule not in ("waves", "refill"):
+            raise ValueError(f"`schedule` must be 'waves' or 'refill', but is {schedule!r}")
+        if schedule == "waves" and len(input_ids) > self.talker.max_batch:
             raise ValueError(f"generate_stream: {len(input_ids)} requests exceed max_batch {self.talker.max_batch}")
         embeds, mask, trailing, pad = self.assemble_prompts(input_ids, languages, speakers, instruct_ids,
                                                             non_streaming_mode, ref_ids, voice_clone_prompt)
@@ -372,7 +379,10 @@ class Qwen3TTSForConditionalGeneration:
                                                   subtalker_top_k=subtalker_top_k, subtalker_top_p=subtalker_top_p,
                                                   subtalker_temperature=subtalker_temperature, eos_token_id=eos,
                                                   repetition_penalty=repetition_penalty, suppress_tokens=suppress,
-                                                  seed=kwargs.get("seed")):
+                                                  seed=kwargs.get("seed"), schedule=schedule):
+            if schedule == "refill":
+                yield packet
+                continue
             yield split_packet_at_eos(packet, alive, eos)
             if not any(alive):
                 return
@@ -695,11 +705,18 @@ class Qwen3TTSModel:
     # ---- streaming output (no reference counterpart: qwen3_tts_model.py:513-515 "only simulates streaming text input")
     @torch.no_grad()
     def stream_custom_voice(self, text, speaker, language=None, instruct=None, non_streaming_mode: bool = False,
-                            packet_frames: int = 4, left_context_size: int = 25, **kwargs):
+                            packet_frames: int = 4, left_context_size: int = 25, schedule: Optional[str] = None, **kwargs):
         """`generate_custom_voice` as a generator of PCM packets: yields (list of np.float32 arrays, one per request --
         empty once that request has finished --, sample_rate) every `packet_frames` frames (80 ms each).  The codes come
         from `generate_stream`; each packet is decoded with `left_context_size` frames of context, i.e. exactly the
-        reference's `chunked_decode(chunk_size=packet_frames, left_context_size=...)` rule applied incrementally."""
+        reference's `chunked_decode(chunk_size=packet_frames, left_context_size=...)` rule applied incrementally.
+
+        `schedule="refill"`: any number of texts on the talker's `max_batch` rows, as `generate_custom_voice(schedule="refill")`
+        schedules them, each request's audio streamed while the others run: a request's array is empty while it is queued, in a
+        packet in which it gained no frame, and once it has finished.  Every talker row owns a slot of the codec's state-carrying
+        decoder (`CodecDecoderEngine.stream_push_rows`), which decodes only the new frames of a packet; `left_context_size` is NOT
+        used under this schedule, and a request's concatenated audio equals the whole-sequence `forward` of its codes, not the
+        chunked rule.  The codec must have been built with a `max_batch` of at least the talker's."""
         if self.model.tts_model_type != "custom_voice":
             raise self._unsupported("stream_custom_voice")
         texts = self._ensure_list(text)
@@ -718,9 +735,42 @@ class Qwen3TTSModel:
         self._validate_speakers(speakers)
         input_ids = self._tokenize_texts([self._build_assistant_text(t) for t in texts])
         gen_kwargs = self._merge_generate_kwargs(**kwargs)
+        if schedule is not None:
+            gen_kwargs["schedule"] = schedule
         dec = self.model.speech_tokenizer.model.decoder
-        stream = dec.stream(left_context_size)
         cb = dec.config.codebook_size
+        if schedule == "refill":
+            rows = self.model.talker.max_batch
+            if dec.max_batch < rows:
+                raise ValueError(f"stream_custom_voice(schedule='refill'): the codec decoder's max_batch ({dec.max_batch}) is smaller than "
+                                 f"the talker's ({rows}); every talker row needs a slot of the codec stream")
+            sr = int(self.model.speech_tokenizer.model.output_sample_rate)
+            dec.stream_begin(rows)
+            for record in self.model.generate_stream(input_ids=input_ids, instruct_ids=self._instruct_ids(instructs), languages=languages,
+                                                     speakers=speakers, non_streaming_mode=non_streaming_mode,
+                                                     packet_frames=packet_frames, **gen_kwargs):
+                started = [e.row for e in record.rows if e.first]
+                if started:
+                    dec.stream_reset_rows(started)
+                live = [e for e in record.rows if e.codes.shape[0] > 0]
+                if not live:
+                    continue
+                k = max(int(e.codes.shape[0]) for e in live)
+                # a row that gained fewer frames than the packet has finished: it is padded with code 0, its extra samples are dropped,
+                # and its slot is reset before the next request uses it
+                if any(int(e.codes.shape[0]) < k and not e.last for e in live):
+                    raise RuntimeError("stream_custom_voice: a running row fell behind its packet")
+                batch = torch.zeros(len(live), k, live[0].codes.shape[-1], dtype=torch.long, device=self.device)
+                for m, e in enumerate(live):
+                    batch[m, : e.codes.shape[0]] = e.codes.clamp(min=0, max=cb - 1)
+                wav = dec.stream_push_rows([e.row for e in live], batch.transpose(1, 2))[:, 0]
+                up = wav.shape[-1] // k
+                out = [np.zeros(0, np.float32) for _ in texts]
+                for m, e in enumerate(live):
+                    out[e.request] = wav[m, : int(e.codes.shape[0]) * up].cpu().numpy().astype(np.float32)
+                yield out, sr
+            return
+        stream = dec.stream(left_context_size)
         for parts in self.model.generate_stream(input_ids=input_ids, instruct_ids=self._instruct_ids(instructs), languages=languages,
                                                 speakers=speakers, non_streaming_mode=non_streaming_mode,
                                                 packet_frames=packet_frames, **gen_kwargs):

@@ -38,6 +38,24 @@ class TalkerGenerateOutput:
     logits_trace: Optional[torch.Tensor] = None  # teacher forcing only: (n_steps, B, vocab) raw cb-0 logits of `logit_steps`
 
 
+@dataclass
+class RefillRow:
+    """One row's share of a `RefillPacket`."""
+    request: int               # index of the request in the list given to `generate_stream`
+    row: int                   # the row (= codec slot) the request occupies
+    codes: torch.Tensor        # (k, G) int64: the frames the request gained in this packet (a copy; k may be 0 when `last`)
+    first: bool                # the request started with this packet: whatever the row held before belongs to another request
+    last: bool                 # the request finished: its frames end here (first eos in codebook 0, or its own limit)
+    hidden: Optional[torch.Tensor] = None        # (k, H) float32 `past_hidden` of these frames, when asked for
+
+
+@dataclass
+class RefillPacket:
+    """What `generate_stream(..., schedule="refill")` yields after every packet of the running stream: one entry per row whose occupant
+    gained frames or finished in it."""
+    rows: List[RefillRow]
+
+
 _SKIP_PREFIXES = ("speaker_encoder.",)
 
 
@@ -445,10 +463,25 @@ class TalkerEngine:
                         subtalker_top_k: Optional[int] = 50, subtalker_top_p: Optional[float] = 1.0,
                         subtalker_temperature: Optional[float] = 0.9, eos_token_id: Optional[int] = None,
                         repetition_penalty: float = 1.05, suppress_tokens: Optional[List[int]] = None,
-                        seed: Optional[int] = None, **unused):
+                        seed: Optional[int] = None, schedule: str = "waves", **unused):
         """Streaming OUTPUT (include/qtts.h `qtts_talker_stream_*`): a generator that yields `codes[:, f0:f1]` (B, k, G)
         int64 device tensors, k <= packet_frames, as the frames are produced; same arguments (per-request sequences included) and the
-        same frames as `generate`.  Closing the generator early abandons the request.  Holds the engine lock while active."""
+        same frames as `generate`.  Closing the generator early abandons the request.  Holds the engine lock while active.
+
+        `schedule="refill"`: any number of requests on `max_batch` rows, scheduled as `generate(schedule="refill")` schedules them (same
+        admission rule, per-row table and seed rules: `_refill_stream`); yields one `RefillPacket` per packet of the running stream
+        instead of a block of codes.  Concatenating a request's packets gives exactly the codes `generate(schedule="refill")` returns
+        for it."""
+        if schedule == "refill":
+            yield from self._refill_stream(inputs_embeds, attention_mask, trailing_text_hidden, tts_pad_embed, packet_frames=packet_frames,
+                                           max_new_tokens=max_new_tokens, min_new_tokens=min_new_tokens, do_sample=do_sample, top_k=top_k,
+                                           top_p=top_p, temperature=temperature, subtalker_dosample=subtalker_dosample,
+                                           subtalker_top_k=subtalker_top_k, subtalker_top_p=subtalker_top_p,
+                                           subtalker_temperature=subtalker_temperature, eos_token_id=eos_token_id,
+                                           repetition_penalty=repetition_penalty, suppress_tokens=suppress_tokens, seed=seed)
+            return
+        if schedule != "waves":
+            raise ValueError(f"`schedule` must be 'waves' or 'refill', but is {schedule!r}")
         c = self.config
         if inputs_embeds.dim() != 3 or inputs_embeds.shape[-1] != c.hidden_size:
             raise ValueError(f"inputs_embeds must be (B, T, {c.hidden_size})")
@@ -600,19 +633,21 @@ class TalkerEngine:
         self._open = None
         return int(nf.value)
 
-    def _generate_refill(self, inputs_embeds: torch.Tensor, attention_mask: torch.Tensor, trailing_text_hidden: torch.Tensor,
-                         tts_pad_embed: torch.Tensor, max_new_tokens=2048, min_new_tokens=2, do_sample=True, top_k=50, top_p=1.0,
-                         temperature=0.9, subtalker_dosample=True, subtalker_top_k=50, subtalker_top_p=1.0, subtalker_temperature=0.9,
-                         eos_token_id: Optional[int] = None, repetition_penalty=1.05, suppress_tokens: Optional[List[int]] = None,
-                         output_hidden_states: bool = True, seed=None, packet_frames: int = 4, **unused) -> TalkerGenerateOutput:
-        """`generate(..., schedule="refill")`: any number of requests on `max_batch` rows.  The rows start with the requests of the
-        longest prompts; the stream runs in packets of `packet_frames` frames; after each packet the finished rows are retired (their
-        frames copied out, cut at the first eos in codebook 0) and every queued request that fits -- prompt no longer than the stream's
-        position, position + its limit inside max_seq -- is admitted, longest prompt first, in one `stream_admit`.  When requests remain
-        but none fits and every row has finished, the stream ends and a fresh one begins with the remainder.  Always runs on the per-row
-        table (scalars are broadcast; seeds as in `_row_table`: a list is per request, one integer s gives request i the seed s + i, none
-        draws fresh ones), so a request's codes do not depend on when or where it was admitted.  Returns the requests in the order
-        given, in `generate`'s structure: codes (N, F, G) with eos in codebook 0 behind a request's last frame, tokens (N, F + 1)."""
+    def _refill_stream(self, inputs_embeds: torch.Tensor, attention_mask: torch.Tensor, trailing_text_hidden: torch.Tensor,
+                       tts_pad_embed: torch.Tensor, max_new_tokens=2048, min_new_tokens=2, do_sample=True, top_k=50, top_p=1.0,
+                       temperature=0.9, subtalker_dosample=True, subtalker_top_k=50, subtalker_top_p=1.0, subtalker_temperature=0.9,
+                       eos_token_id: Optional[int] = None, repetition_penalty=1.05, suppress_tokens: Optional[List[int]] = None,
+                       output_hidden_states: bool = False, seed=None, packet_frames: int = 4, **unused):
+        """The refill schedule, packet by packet (`generate_stream(..., schedule="refill")`; `generate(..., schedule="refill")` collects
+        what this yields): any number of requests on `max_batch` rows.  The rows start with the requests of the longest prompts; the
+        stream runs in packets of `packet_frames` frames; after each packet every row whose occupant gained frames or finished is
+        reported in one `RefillPacket` (the new frames copied out, cut at the first eos in codebook 0 or at the request's limit), the
+        finished rows are retired and every queued request that fits -- prompt no longer than the stream's position, position + its
+        limit inside max_seq -- is admitted, longest prompt first, in one `stream_admit`.  When requests remain but none fits and every
+        row has finished, the stream ends and a fresh one begins with the remainder.  Always runs on the per-row table (scalars are
+        broadcast; seeds as in `_row_table`: a list is per request, one integer s gives request i the seed s + i, none draws fresh
+        ones), so a request's codes do not depend on when or where it was admitted.  Closing the generator closes the stream;
+        `last_refill` is filled either way.  Holds the engine lock while active."""
         c, dev = self.config, self.device
         if inputs_embeds.dim() != 3 or inputs_embeds.shape[-1] != c.hidden_size:
             raise ValueError(f"inputs_embeds must be (B, T, {c.hidden_size})")
@@ -642,53 +677,87 @@ class TalkerEngine:
         pad = tts_pad_embed.to(dev, torch.float32).reshape(-1)
         if pad.numel() != H:
             raise ValueError("tts_pad_embed must have H elements")
-        G, mb = c.num_code_groups, self.max_batch
+        mb = self.max_batch
         max_row = max(int(rows[i].max_new_tokens) for i in range(N))
-        out_codes, out_hidden = [None] * N, [None] * N
         queue = sorted(range(N), key=lambda i: (-lens[i], i))
         st = dict(streams=0, admit_calls=0, admitted_rows=0, frames_run=0, row_frames=0, graph_captures=0)
-        caps0 = self.stats()["graph_captures"]
 
         def group(idx):
             Tg = max(lens[i] for i in idx)
             tab = (_lib.RowSamplingC * len(idx))(*[rows[i] for i in idx])
             return emb[idx][:, T - Tg:], [Tg - lens[i] for i in idx], trail[idx], tab
 
-        while queue:
-            # a fresh stream: the longest prompt first, then the longest of the rest whose limits fit behind it
-            T0 = lens[queue[0]]
-            first = [i for i in queue if T0 + int(rows[i].max_new_tokens) <= self.max_seq][:mb]
-            queue = [i for i in queue if i not in first]
-            e, npd, tr, tab = group(first)
-            codes, hidden = self.stream_open(e, npd, tr, pad, tab, max_row, eos, suppress_tokens, output_hidden_states)
-            st["streams"] += 1
-            slot = list(first)
+        with self._lock:
+            caps0 = self.stats()["graph_captures"]
             try:
-                while any(r is not None for r in slot):
-                    self.stream_step(packet_frames)
-                    unfinished, frames, kv_len = self.stream_rows()
-                    for b, r in enumerate(slot):
-                        if r is not None and not unfinished[b]:
-                            out_codes[r] = codes[b, :frames[b]].clone()
-                            out_hidden[r] = hidden[b, :frames[b]].clone() if hidden is not None else None
-                            st["row_frames"] += frames[b]
-                            slot[b] = None
-                    free = [b for b, r in enumerate(slot) if r is None]
-                    take = [i for i in queue if lens[i] <= kv_len and kv_len + int(rows[i].max_new_tokens) <= self.max_seq][:len(free)]
-                    if take:
-                        e, npd, tr, tab = group(take)
-                        self.stream_admit(free[:len(take)], e, npd, tr, tab)
-                        for b, r in zip(free, take):
-                            slot[b] = r
-                        queue = [i for i in queue if i not in take]
-                s1 = self.stats()
-                st["admit_calls"] += s1["admit_calls"]
-                st["admitted_rows"] += s1["admitted_rows"]
+                while queue:
+                    # a fresh stream: the longest prompt first, then the longest of the rest whose limits fit behind it
+                    T0 = lens[queue[0]]
+                    first = [i for i in queue if T0 + int(rows[i].max_new_tokens) <= self.max_seq][:mb]
+                    queue = [i for i in queue if i not in first]
+                    e, npd, tr, tab = group(first)
+                    codes, hidden = self.stream_open(e, npd, tr, pad, tab, max_row, eos, suppress_tokens, output_hidden_states)
+                    st["streams"] += 1
+                    slot, seen, fresh = list(first), [0] * len(first), set(first)
+                    try:
+                        while any(r is not None for r in slot):
+                            self.stream_step(packet_frames)
+                            unfinished, frames, kv_len = self.stream_rows()
+                            packet = []
+                            for b, r in enumerate(slot):
+                                if r is None:
+                                    continue
+                                done, k0, k1 = not unfinished[b], seen[b], frames[b]
+                                if k1 > k0 or done:
+                                    packet.append(RefillRow(request=r, row=b, codes=codes[b, k0:k1].clone(), first=r in fresh, last=done,
+                                                            hidden=hidden[b, k0:k1].clone() if hidden is not None else None))
+                                    fresh.discard(r)
+                                    seen[b] = k1
+                                if done:
+                                    st["row_frames"] += k1
+                                    slot[b] = None
+                            yield RefillPacket(packet)
+                            free = [b for b, r in enumerate(slot) if r is None]
+                            take = [i for i in queue if lens[i] <= kv_len and kv_len + int(rows[i].max_new_tokens) <= self.max_seq][:len(free)]
+                            if take:
+                                e, npd, tr, tab = group(take)
+                                self.stream_admit(free[:len(take)], e, npd, tr, tab)
+                                for b, r in zip(free, take):
+                                    slot[b], seen[b] = r, 0
+                                    fresh.add(r)
+                                queue = [i for i in queue if i not in take]
+                    finally:
+                        s1 = self.stats()
+                        st["admit_calls"] += s1["admit_calls"]
+                        st["admitted_rows"] += s1["admitted_rows"]
+                        st["frames_run"] += self.stream_close()
             finally:
-                st["frames_run"] += self.stream_close()
-        st["graph_captures"] = self.stats()["graph_captures"] - caps0
-        st["occupancy"] = st["row_frames"] / max(1, st["frames_run"] * mb)
-        self.last_refill = st
+                st["graph_captures"] = self.stats()["graph_captures"] - caps0
+                st["occupancy"] = st["row_frames"] / max(1, st["frames_run"] * mb)
+                self.last_refill = st
+
+    def _generate_refill(self, inputs_embeds: torch.Tensor, attention_mask: torch.Tensor, trailing_text_hidden: torch.Tensor,
+                         tts_pad_embed: torch.Tensor, max_new_tokens=2048, min_new_tokens=2, do_sample=True, top_k=50, top_p=1.0,
+                         temperature=0.9, subtalker_dosample=True, subtalker_top_k=50, subtalker_top_p=1.0, subtalker_temperature=0.9,
+                         eos_token_id: Optional[int] = None, repetition_penalty=1.05, suppress_tokens: Optional[List[int]] = None,
+                         output_hidden_states: bool = True, seed=None, packet_frames: int = 4, **unused) -> TalkerGenerateOutput:
+        """`generate(..., schedule="refill")`: the packets of `_refill_stream` (its arguments and schedule) collected per request.
+        Returns the requests in the order given, in `generate`'s structure: codes (N, F, G) with eos in codebook 0 behind a request's
+        last frame, tokens (N, F + 1)."""
+        c, dev = self.config, self.device
+        eos = c.codec_eos_token_id if eos_token_id is None else int(eos_token_id)
+        N, G, H = int(inputs_embeds.shape[0]), c.num_code_groups, c.hidden_size
+        parts, hparts = [[] for _ in range(N)], [[] for _ in range(N)]
+        for packet in self._refill_stream(inputs_embeds, attention_mask, trailing_text_hidden, tts_pad_embed, max_new_tokens=max_new_tokens,
+                                          min_new_tokens=min_new_tokens, do_sample=do_sample, top_k=top_k, top_p=top_p,
+                                          temperature=temperature, subtalker_dosample=subtalker_dosample, subtalker_top_k=subtalker_top_k,
+                                          subtalker_top_p=subtalker_top_p, subtalker_temperature=subtalker_temperature, eos_token_id=eos,
+                                          repetition_penalty=repetition_penalty, suppress_tokens=suppress_tokens,
+                                          output_hidden_states=output_hidden_states, seed=seed, packet_frames=packet_frames):
+            for e in packet.rows:
+                parts[e.request].append(e.codes)
+                hparts[e.request].append(e.hidden)
+        out_codes = [torch.cat(p) for p in parts]
         F = max([1] + [int(x.shape[0]) for x in out_codes])
         codes_all = torch.zeros(N, F, G, dtype=torch.int64, device=dev)
         codes_all[:, :, 0] = eos
@@ -699,7 +768,7 @@ class TalkerEngine:
             codes_all[i, :n] = out_codes[i]
             tokens[i, :n] = out_codes[i][:, 0]
             if hidden_all is not None:
-                hidden_all[i, :n] = out_hidden[i]
+                hidden_all[i, :n] = torch.cat(hparts[i])
         return TalkerGenerateOutput(codes=codes_all, hidden=hidden_all, tokens=tokens, n_frames=F)
 
     @_lib.locked
