@@ -52,7 +52,10 @@ const char* qtts_last_error(void);
  * qtts_talker_stream_begin_rows, qtts_talker_stats.graph_captures / row_table_last (appended); 15: + qtts_talker_stream_begin_admitting,
  * qtts_talker_stream_admit, qtts_talker_stream_rows, qtts_talker_stats.admit_calls / admitted_rows (two words IN FRONT of row_table_last:
  * the struct's tail moved by 8 bytes); still 15: + qtts_codec_stream_reset_rows, qtts_codec_stream_push_rows -- two entry points
- * added, no signature and no struct layout changed; a binding that needs them finds out by looking the symbols up). */
+ * added, no signature and no struct layout changed; a binding that needs them finds out by looking the symbols up; still 15:
+ * + qtts_talker_stream_begin_admitting_rows, qtts_talker_stream_row_lens, qtts_talker_stream_mode -- three entry points added, no
+ * signature and no struct layout changed: qtts_talker_stats is byte for byte what it was, so a v15 binding keeps working and one that
+ * needs the new calls finds out by looking the symbols up). */
 #define QTTS_ABI_VERSION 15
 int qtts_abi_version(void);
 
@@ -483,6 +486,31 @@ int qtts_talker_stream_admit(qtts_talker* t, int32_t n_new, const int32_t* rows_
                              const int32_t* n_pad_host, const float* trailing_dev, int32_t Tt, const qtts_row_sampling* settings_host,
                              void* stream);
 int qtts_talker_stream_rows(qtts_talker* t, int32_t* unfinished_host, int32_t* frames_host, int32_t* kv_len_host);
+
+/* Per-row KV positions: an admitting stream that never has to drain.  qtts_talker_stream_begin_admitting_rows takes the arguments of
+ * qtts_talker_stream_begin_admitting and opens a stream whose rows each carry their OWN KV length: an admitted request's prompt goes to
+ * slots [0, T) of the row it takes (left-padded inside the group's T as before), the row's length restarts at T and grows by one per
+ * frame step while its occupant is unfinished; a finished row's length is frozen until the row is re-occupied.  Nothing of a previous
+ * occupant is read: its keys lie at or above the new length, or are overwritten.  The decode attention of row b walks row b's keys only,
+ * and the split-KV span of a frame step is the bucket of the longest RUNNING row: it goes up when a long prompt is admitted and down
+ * when a long row retires (one captured graph per bucket visited, cached).  The stream's stop condition is "no row unfinished" alone:
+ * no step count and no position bounds it.
+ *   stream_admit  on such a stream: the refusals tied to the stream's position are gone.  The one QTTS_ERR_LIMIT of its own is
+ *                 T + max_new_tokens > max_seq for a row of the group (naming the row, before anything is launched; a refused call
+ *                 changes no row).  Row not finished / listed twice / out of range, max_row_tokens, the trailing capacity and the
+ *                 settings checks are refused as on a shared-position stream.
+ *   stream_rows   kv_len_host reports the length of the longest row whose occupant is still running (0: none).
+ *   stream_row_lens  lens_host[b] = row b's KV length (a finished row: the frozen one).  QTTS_ERR_STATE without such a stream open.
+ *                 Synchronises the stream the stream was begun on.
+ * Every other mode -- the shared-position stream, the scalar paths -- is bit for bit what it was. */
+int qtts_talker_stream_begin_admitting_rows(qtts_talker* t, const qtts_row_sampling* rows_host, int32_t n_rows, int32_t max_row_tokens,
+                                            int32_t eos_token_id, const int32_t* suppress_host, int32_t n_suppress, int64_t* codes_dev,
+                                            float* hidden_dev, void* stream);
+int qtts_talker_stream_row_lens(qtts_talker* t, int32_t* lens_host /* (B) */);
+/* Whether the open or last stream carries per-row positions (0 | 1; any later generation call clears it), and the largest KV length a
+ * row of it was seen at (0 without such a stream).  These are statistics, but qtts_talker_stats keeps its layout under ABI 15: they
+ * have a call of their own. */
+int qtts_talker_stream_mode(qtts_talker* t, int32_t* row_positions_host, int32_t* max_row_len_host);
 
 /* Test/diagnostic hooks (device -> caller device buffers, after prefill / a generate call). */
 int qtts_talker_debug_logits(qtts_talker* t, float* logits_dev /* (B, vocab) */, void* stream);

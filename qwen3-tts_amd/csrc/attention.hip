@@ -451,7 +451,9 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(AttnDecodeParams p) {
             x0v[r] = src[lane]; x1v[r] = src[lane + 64];
         }
     }
-    const int S0 = p.len_dev ? *p.len_dev : p.len_static;   // KV length before this step
+    int S0 = attn_len(p, b);         // KV length before this step
+    // per-row positions: an idle row keeps its frozen length while the span follows the occupied rows; its scores must stay inside sc[]
+    if (p.len_stride) S0 = min(S0, p.max_len - p.n_new);
     const int npad = p.n_pad ? p.n_pad[b] : 0;
     const int done = p.done_flag ? *p.done_flag : 0;
     const int S1 = S0 + p.n_new;               // total keys
@@ -971,7 +973,7 @@ __global__ __launch_bounds__(256) void attn_tk_kernel(AttnDecodeParams p) {
     load_chunk(vR[0], vc, c0s);
     const bool deep = p.max_len > 64 && cps > 1;
     if (deep) { load_chunk(kR[1], kc, c0s + 1); load_chunk(vR[1], vc, c0s + 1); }
-    const int S0 = p.len_dev ? *p.len_dev : p.len_static;   // KV length before this step
+    const int S0 = attn_len(p, b);   // KV length before this step
     const int npad = p.n_pad ? p.n_pad[b] : 0;
     const int done = p.done_flag ? *p.done_flag : 0;
     const int S1 = S0 + 1;                                  // total keys
@@ -999,6 +1001,9 @@ __global__ __launch_bounds__(256) void attn_tk_kernel(AttnDecodeParams p) {
         }
         if (vi >= GQ) {
             const KVT h0 = kv_cast<KVT>(x0), h1 = kv_cast<KVT>(x1);
+            // (no `(S0 >> 4) < pages_per_seq` guard here, unlike attn_tk16_kernel: the append relies on the host's invariant -- a step at
+            // capacity is refused before it is launched, and with per-row lengths a row admitted at T under the limit L never passes
+            // T + L - 2 <= max_seq - 2, frozen or running: talker_engine.hip, admit)
             if (wave == 0 && split == 0) {
                 const int page = CT ? b * p.kv.pages_per_seq + (S0 >> 4) : p.kv.page_table[b * p.kv.pages_per_seq + (S0 >> 4)];
                 const size_t o = ((((size_t)p.layer * p.kv.n_pages + page) * p.kv.nkv + kvh) * 16 + (S0 & 15)) * HD;
@@ -1229,7 +1234,7 @@ __global__ __launch_bounds__(256) void attn_tk16_kernel(AttnDecodeParams p) {
     u32x4 kA[NB][4], kB[NB][4], vT[NB][8];
 #pragma unroll
     for (int n = 0; n < NB; ++n) load_block(kA[n], kB[n], vT[n], b0s + wave + 4 * n);
-    const int S0 = p.len_dev ? *p.len_dev : p.len_static;   // KV length before this step = position of the new key
+    const int S0 = attn_len(p, b);   // KV length before this step = position of the new key
     const int npad = p.n_pad ? p.n_pad[b] : 0;
     const int done = p.done_flag ? *p.done_flag : 0;
     if (done) return;

@@ -175,7 +175,7 @@ __device__ __forceinline__ void attn_gq16_body(const AttnDecodeParams& p, float*
     };
 
     const int nsplit = gridDim.y, split = blockIdx.y;
-    const int S0 = p.len_dev ? *p.len_dev : p.len_static;    // KV length before this step = position of the first new key
+    const int S0 = attn_len(p, b);    // KV length before this step = position of the first new key
     const int npad = p.n_pad ? p.n_pad[b] : 0;
     const int done = p.done_flag ? *p.done_flag : 0;
     if (done) return;
@@ -290,7 +290,7 @@ __device__ __forceinline__ void attn_gqv_body(const AttnDecodeParams& p, float* 
     const KVT* vc = reinterpret_cast<const KVT*>(p.kv.v);
     const int pps = p.kv.pages_per_seq;
     const int nsplit = gridDim.y, split = blockIdx.y;
-    const int S0 = p.len_dev ? *p.len_dev : p.len_static;
+    const int S0 = attn_len(p, b);
     const int npad = p.n_pad ? p.n_pad[b] : 0;
     const int done = p.done_flag ? *p.done_flag : 0;
     if (done) return;

@@ -13,6 +13,9 @@ struct StepState {
     int* final_count;   // n_generated at that moment
     int* unfinished;    // [B]
     int* frame_serial;  // optional: +1 per frame step, never reset (the hand-off tags of attention.hip's cp_attn_o_kernel derive from it)
+    // per-row positions (qtts_talker_stream_begin_admitting_rows): [B] KV lengths, one per row, or null.  Set: a frame step advances the
+    // length of every row that is still unfinished and leaves kv_len alone; a finished row's length freezes until the row is re-occupied.
+    int* row_len;
 };
 void launch_sample_finish(const StepState& s, int B, int max_new_tokens, hipStream_t st);
 

@@ -245,7 +245,13 @@ struct AttnDecodeParams {
     // instead of running sinf / cosf behind the arrival of the qkv row
     const float* rope_cs; int rope_cs_n;
     int force_gq;                // 1: the general family (attn_gq.h) also for head_dim 128 with a group <= 2 (QTTS_ATTN_GQ=1: A/B, goldens)
+    // per-row positions (qtts_talker_stream_begin_admitting_rows): sequence b reads its KV length from len_dev[b * len_stride].  0: every
+    // sequence reads word 0 (one position per stream); 1: an array of B lengths.  Everything a kernel derives from the length -- RoPE angle,
+    // append slot, block range, validity mask, the split that owns the new key -- is then the row's own.
+    int len_stride;
 };
+// the KV length of sequence b before this step (decode attention kernels)
+__device__ __forceinline__ int attn_len(const AttnDecodeParams& p, int b) { return p.len_dev ? p.len_dev[b * p.len_stride] : p.len_static; }
 void launch_attn_decode(const AttnDecodeParams& p, hipStream_t st);
 // whether launch_attn_decode runs the general family (attn_gq.h: head_dim 64 | 128, group 1..8) for this call: every shape the older
 // kernels do not have (they keep head_dim 128 with a group <= 2), or force_gq

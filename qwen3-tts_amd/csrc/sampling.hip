@@ -740,17 +740,23 @@ void launch_sample(const SampleParams& p, hipStream_t st) {
 
 // ---------------------------------------------------------------------------------- loop bookkeeping
 // After every row sampled token #n: n_generated++, kv_len++, and latch `done` exactly where HF's
-// stopping criteria would break (all rows finished, or max_new_tokens reached).
+// stopping criteria would break (all rows finished, or max_new_tokens reached).  With per-row positions (st.row_len) the rows
+// that are still unfinished advance their own length instead; the row that has just finished keeps the length its last key was
+// written at, so an idle row writes the same slot of its own pages again and again and nothing else.
 __global__ void sample_finish_kernel(StepState st, int B, int max_new_tokens) {
     if (*st.done) return;
     if (threadIdx.x == 0) {
         const int n = *st.n_generated + 1;
         *st.n_generated = n;
         *st.gen_step += 1;
-        *st.kv_len += 1;
+        if (!st.row_len) *st.kv_len += 1;
         if (st.frame_serial) *st.frame_serial += 1;
         int any = 0;
-        for (int b = 0; b < B; ++b) any |= st.unfinished[b];
+        for (int b = 0; b < B; ++b) {
+            const int u = st.unfinished[b];
+            any |= u;
+            if (st.row_len && u) st.row_len[b] += 1;
+        }
         if (n >= max_new_tokens || !any) { *st.done = 1; *st.final_count = n; }
     }
 }

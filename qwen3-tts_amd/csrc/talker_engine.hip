@@ -73,6 +73,16 @@ struct qtts_talker {
     // admission into a running stream (qtts_talker_stream_admit): the group's row map and local pads, and the staging rows of its
     // last-position hidden, past_hidden and logits (the running rows' buffers are not touched)
     DevBuf adm_rows_d, adm_npad_d, adm_x, adm_ph, adm_lg;
+    // per-row positions (qtts_talker_stream_begin_admitting_rows): every row's own KV length, read by the decode attention with stride 1
+    // and advanced by sample_finish_kernel for the unfinished rows; the host's mirror of it and of the unfinished flags (refreshed with
+    // every poll: set at admission, plus one per step while unfinished) picks the split-KV bucket of the longest running row
+    // (the lengths live in `ints` behind the unfinished flags: one copy of that block is a poll's done word, flags and lengths)
+    int* row_len_p = nullptr;
+    std::vector<int> ints_h;
+    bool row_pos = false;
+    std::vector<int> row_len_h, row_unf_h;
+    static constexpr int INTS_WORDS = 64 + 64 + 64;      // loop state | unfinished[64] | row_len[64]
+    int max_row_len = 0;                // the largest length a running row had at a poll of the open / last stream
     StepState ss;
     int B = 0, T0 = 0, Tt = 0, gen_cap = 0;
     // graph
@@ -87,7 +97,7 @@ struct qtts_talker {
         int do_sample, top_k, sub_do_sample, sub_top_k;
         float top_p, temperature, rep, sub_top_p, sub_temperature;
         const void *codes, *hidden, *trailing, *tts_pad, *generated;
-        int row_mode, row_fast_t, row_fast_c;
+        int row_mode, row_fast_t, row_fast_c, row_pos;
         bool operator==(const GraphKey& o) const { return memcmp(this, &o, sizeof(GraphKey)) == 0; }
     } graph_key;
     GraphKey make_key(const qtts_sampling& sp, int eos, int min_new, int max_new, int max_frames, const void* codes, const void* hidden) const {
@@ -100,6 +110,7 @@ struct qtts_talker {
             key.sub_top_k = sp.subtalker_top_k; key.top_p = sp.top_p; key.temperature = sp.temperature; key.rep = sp.repetition_penalty;
             key.sub_top_p = sp.subtalker_top_p; key.sub_temperature = sp.subtalker_temperature;
         }
+        key.row_pos = row_pos ? 1 : 0;
         key.codes = codes; key.hidden = hidden; key.trailing = trailing.p; key.tts_pad = tts_pad.p; key.generated = generated.p;
         return key;
     }
@@ -403,6 +414,7 @@ struct qtts_talker {
         a.len_dev = len_dev; a.len_static = len_static; a.kv = kv; a.layer = layer; a.out = attb; a.ldo = d.qd;
         a.max_len = max_len; a.done_flag = ss.done;
         a.rope_cs = rope_cs; a.rope_cs_n = rope_cs_n; a.force_gq = attn_gq_env ? 1 : 0;
+        a.len_stride = (len_dev && row_pos) ? 1 : 0;
         if (len_dev && attn_nsplit_active > 1) {     // talker, long sequences: split-KV over the LIVE length's bucket, not the capacity
             a.nsplit = attn_nsplit_active; a.part = attn_part.as<float>(); a.max_len = attn_span_active;
         }
@@ -578,6 +590,26 @@ struct qtts_talker {
         if (long_mode(kv_len_after)) { attn_span_active = span_bucket(kv_len_after); attn_nsplit_active = nsplit_for(attn_span_active); }
         else { attn_span_active = 0; attn_nsplit_active = 1; }
     }
+    // per-row positions: the host's mirror of the rows' lengths and unfinished flags, read back on `st` (synchronises it)
+    // (returns the done word of the same copy: a poll in this mode is still ONE device-to-host copy)
+    int mirror_rows(hipStream_t st) {
+        row_len_h.resize(B); row_unf_h.resize(B); ints_h.resize(INTS_WORDS);
+        QTTS_CHECK_HIP(hipMemcpyAsync(ints_h.data(), ints.p, (size_t)INTS_WORDS * 4, hipMemcpyDeviceToHost, st));
+        QTTS_CHECK_HIP(hipStreamSynchronize(st));
+        for (int b = 0; b < B; ++b) { row_unf_h[b] = ints_h[64 + b]; row_len_h[b] = ints_h[64 + 64 + b]; }
+        for (int b = 0; b < B; ++b) max_row_len = std::max(max_row_len, row_len_h[b]);      // (a frozen length was reached while running)
+        return ints_h[3];
+    }
+    // the longest length among the rows whose occupant is still running (0: none)
+    int longest_row() const {
+        int m = 0;
+        for (int b = 0; b < (int)row_len_h.size(); ++b)
+            if (row_unf_h[b]) m = std::max(m, row_len_h[b]);
+        return m;
+    }
+    // ... and the largest length any of them can reach within `burst` more steps: a finished row's length is frozen, so it keeps no
+    // bucket alive, and the bucket goes down again when the long row retires
+    int row_reach(int burst) const { return std::min(cfg.max_seq, std::max(1, longest_row() + burst)); }
     bool any_graph() const { return graph_exec != nullptr || !graph_long.empty(); }
     // the captured graph for the mode a burst ending at `kv_len_after` keys runs in, capturing `step` (which is NOT executed by
     // the capture) on first use
@@ -882,7 +914,7 @@ void qtts_talker::finalize() {
     act.alloc((size_t)R * td.I * 4); logits.alloc((size_t)R * c.vocab_size * 4); past_hidden.alloc((size_t)R * td.H * 4);
     cp_in.alloc((size_t)R2 * td.H * 4); cp_x.alloc((size_t)R2 * cd.H * 4); cp_qkv.alloc((size_t)R2 * (cd.qd + 2 * cd.kvd) * 4);
     cp_att.alloc((size_t)R2 * cd.qd * 4); cp_act.alloc((size_t)R2 * cd.I * 4); cp_logits.alloc((size_t)(c.num_code_groups - 1) * R * c.cp_vocab_size * 4);     // [pass][row][cp vocab]: every pass keeps its own rows (qtts_talker_debug_cp_logits)
-    cur_tok.alloc(R * 4); sub.alloc((size_t)R * G * 4); ss_rows.alloc((size_t)R2 * 8); ints.alloc(64 * 4 + R * 4);
+    cur_tok.alloc(R * 4); sub.alloc((size_t)R * G * 4); ss_rows.alloc((size_t)R2 * 8); ints.alloc((size_t)INTS_WORDS * 4);
     if (!bf16) {                      // the two halves of a split-K o- / down-projection (decode_layer)
         const size_t hmax = (size_t)std::max(td.H, cd.H);
         sk_part.alloc(2 * 8 * hmax * 4);
@@ -916,6 +948,8 @@ void qtts_talker::finalize() {
     n_pad_d.alloc(R * 4); suppress.alloc(c.vocab_size); seed_d.alloc(8); rows_d.alloc((size_t)R * sizeof(SampleRow));
     QTTS_CHECK_HIP(hipMemset(ss_rows.p, 0, ss_rows.bytes));
     int* ip = ints.as<int>();
+    row_len_p = ip + 64 + 64;
+    QTTS_CHECK_HIP(hipMemset(row_len_p, 0, 64 * 4));
     ss = {ip + 0, ip + 1, ip + 2, ip + 3, ip + 4, ip + 64, ip + 6};
     { const int one = 1; QTTS_CHECK_HIP(hipMemcpy(ss.frame_serial, &one, 4, hipMemcpyHostToDevice)); }       // (0 is the tag of a never-written granule)
     // A/B variant (build.py VARIANTS): in passes 1 .. G-2 the code predictor's layer-0 q|k|v GEMM sees only the pass input row,
@@ -1134,8 +1168,8 @@ void qtts_talker::frame_step(const qtts_sampling& sp, int eos, int min_new, int 
     // ---- talker decode forward (M:1706-1727)
     cur_stack = 0;
     for (int l = 0; l < c.num_hidden_layers; ++l)
-        decode_layer(tl[l], td, x.as<float>(), bf16 ? x16.as<unsigned short>() : nullptr, qkv.as<float>(), att.as<float>(), act.as<float>(), B, 1, kv_t, l, ss.kv_len, 0,
-                     n_pad_d.as<int>(), inv_freq_t.as<float>(), c.max_seq, st, nullptr, 0, l + 1 == c.num_hidden_layers);
+        decode_layer(tl[l], td, x.as<float>(), bf16 ? x16.as<unsigned short>() : nullptr, qkv.as<float>(), att.as<float>(), act.as<float>(), B, 1, kv_t, l,
+                     row_pos ? row_len_p : ss.kv_len, 0, n_pad_d.as<int>(), inv_freq_t.as<float>(), c.max_seq, st, nullptr, 0, l + 1 == c.num_hidden_layers);
     if (!skinny_only) launch_apply_norm(x.as<float>(), td.H, t_norm.as<float>(), td.eps, past_hidden.as<float>(), td.H, B, td.H, ss.done, st,
                                         bf16 ? ph16.as<unsigned short>() : nullptr);
     SkinnyParams h{};
@@ -1369,20 +1403,27 @@ void qtts_talker::admit(int n_new, const int32_t* rows_host, const float* embeds
         if (uf[b]) fail(QTTS_ERR_ARG, b, "its occupant is still unfinished");
         QTTS_REQUIRE(n_pad_host[i] >= 0 && n_pad_host[i] < T, QTTS_ERR_ARG, std::string(who) + ": row " + std::to_string(b) + ": n_pad out of range");
         entries[i] = check_row(settings[i], b, who);
+        if (row_pos) {            // the row restarts at T: the one bound is its own
+            if (T + settings[i].max_new_tokens > cfg.max_seq)
+                fail(QTTS_ERR_LIMIT, b, "the group's padded length T (" + std::to_string(T) + ") + max_new_tokens (" + std::to_string(settings[i].max_new_tokens) + ") exceeds max_seq");
+        } else {
         if (T - n_pad_host[i] > kv_len)
             fail(QTTS_ERR_LIMIT, b, "the prompt (" + std::to_string(T - n_pad_host[i]) + " rows) is longer than the stream's position (" + std::to_string(kv_len) + ")");
         if (kv_len + settings[i].max_new_tokens > cfg.max_seq)
             fail(QTTS_ERR_LIMIT, b, "the stream's position (" + std::to_string(kv_len) + ") + max_new_tokens (" + std::to_string(settings[i].max_new_tokens) + ") exceeds max_seq");
+        }
         if (settings[i].max_new_tokens > g.max_row)
             fail(QTTS_ERR_LIMIT, b, "max_new_tokens (" + std::to_string(settings[i].max_new_tokens) + ") exceeds the stream's max_row_tokens (" + std::to_string(g.max_row) + ")");
         if (Tt_ > Tt) fail(QTTS_ERR_LIMIT, b, "trailing rows (" + std::to_string(Tt_) + ") exceed the stream's trailing capacity (" + std::to_string(Tt) + ")");
         entries[i].origin = gen_step;
-        npad_g[i] = kv_len - T + n_pad_host[i];
+        npad_g[i] = row_pos ? n_pad_host[i] : kv_len - T + n_pad_host[i];
     }
-    if (T > kv_len)       // (every prompt fits, the group's padded length does not)
+    if (!row_pos && T > kv_len)       // (every prompt fits, the group's padded length does not)
         fail(QTTS_ERR_LIMIT, rows_host[0], "the group's padded length T (" + std::to_string(T) + ") is longer than the stream's position (" + std::to_string(kv_len) + ")");
     // ---- from here on the call writes
-    const int H = td.H, V = cfg.vocab_size, M = n_new * T, base = kv_len - T;
+    // per-row positions: the prompt goes to slots [0, T) of the row and the row's length restarts at T -- nothing of the previous occupant
+    // is read again: its keys lie at or above the new length, or are overwritten
+    const int H = td.H, V = cfg.vocab_size, M = n_new * T, base = row_pos ? 0 : kv_len - T;
     bool fast_t = row_fast_t, fast_c = row_fast_c;
     for (auto& e : entries) { fast_t = fast_t && row_fast_talker(e, V); fast_c = fast_c && row_fast_sub(e, cfg.cp_vocab_size); }
     if (fast_t != row_fast_t || fast_c != row_fast_c) {      // an occupant outside the fast samplers' class: the stream's frame graphs bake the class in
@@ -1419,6 +1460,7 @@ void qtts_talker::admit(int n_new, const int32_t* rows_host, const float* embeds
         QTTS_CHECK_HIP(hipMemcpyAsync(n_pad_d.as<int>() + b, &npad_g[i], 4, hipMemcpyHostToDevice, st));
         QTTS_CHECK_HIP(hipMemcpyAsync(rows_d.as<SampleRow>() + b, &entries[i], sizeof(SampleRow), hipMemcpyHostToDevice, st));
         QTTS_CHECK_HIP(hipMemcpyAsync(ss.unfinished + b, &one, 4, hipMemcpyHostToDevice, st));
+        if (row_pos) QTTS_CHECK_HIP(hipMemcpyAsync(row_len_p + b, &T, 4, hipMemcpyHostToDevice, st));
     }
     QTTS_CHECK_HIP(hipMemcpyAsync(ss.done, &zero, 4, hipMemcpyHostToDevice, st));
     // token 0 of the admitted rows only: the talker's sampler on ONE row at a time (every per-row pointer moved to the row; the table's
@@ -1438,6 +1480,7 @@ void qtts_talker::admit(int n_new, const int32_t* rows_host, const float* embeds
     }
     QTTS_CHECK_HIP(hipStreamSynchronize(st));      // (host buffers above must outlive the copies)
     for (int i = 0; i < n_new; ++i) g.tab[rows_host[i]] = entries[i];
+    if (row_pos) mirror_rows(st);
     g.done = 0;
     admit_calls += 1; admitted_rows += n_new;
 }
@@ -1454,6 +1497,7 @@ static void upload_call_state(qtts_talker* t, const qtts_sampling& sp, const Row
         m[suppress_host[i]] = 1;
     }
     t->row_mode = rt != nullptr; t->row_fast_t = rt && rt->fast_t; t->row_fast_c = rt && rt->fast_c;
+    t->row_pos = false; t->ss.row_len = nullptr;       // (per-row positions are a mode of ONE stream: stream_begin_body sets it after this)
     QTTS_CHECK_HIP(hipMemcpyAsync(t->suppress.p, m.data(), V, hipMemcpyHostToDevice, st));
     const unsigned long long seed = sp.seed;
     QTTS_CHECK_HIP(hipMemcpyAsync(t->seed_d.p, &seed, 8, hipMemcpyHostToDevice, st));
@@ -1601,20 +1645,23 @@ static void stream_launch_frames(qtts_talker* t, int n, hipStream_t st) {
     auto& g = t->sg;
     const bool use_graph = t->cfg.use_graph != 0;
     auto poll = [&]() {
+        if (t->row_pos) { g.done = t->mirror_rows(st); return; }
         QTTS_CHECK_HIP(hipMemcpyAsync(&g.done, t->ss.done, 4, hipMemcpyDeviceToHost, st));
         QTTS_CHECK_HIP(hipStreamSynchronize(st));
     };
+    // the KV length the attention mode of the next `burst` steps must hold: the stream's position, or the longest running row's
+    auto reach = [&](int burst) { return t->row_pos ? t->row_reach(burst) : t->T0 + g.launched + burst; };
     int left = std::min(n, g.total - g.launched);
     while (!g.done && left > 0) {
         if (!use_graph) {
-            t->set_attn_mode(t->T0 + g.launched + 1);
+            t->set_attn_mode(reach(1));
             t->frame_step(g.sp, g.eos, g.min_new, g.max_new, g.codes, g.hidden, g.max_frames, st);
             ++g.launched; --left;
             poll();
             continue;
         }
         const int burst = std::min(8, left);
-        hipGraphExec_t ge = t->ensure_graph(t->T0 + g.launched + burst, st, [&] {
+        hipGraphExec_t ge = t->ensure_graph(reach(burst), st, [&] {
             t->frame_step(g.sp, g.eos, g.min_new, g.max_new, g.codes, g.hidden, g.max_frames, st); });
         for (int i = 0; i < burst; ++i) QTTS_CHECK_HIP(hipGraphLaunch(ge, st));
         g.launched += burst; left -= burst;
@@ -1628,8 +1675,13 @@ static void stream_launch_frames(qtts_talker* t, int n, hipStream_t st) {
 // (max_seq), which every admission checks for its own rows.
 static void stream_begin_body(qtts_talker* t, const qtts_sampling* sp, const RowTable* rt, int32_t max_new_tokens, int32_t min_new_tokens,
                               int32_t eos_token_id, const int32_t* suppress_host, int32_t n_suppress, int64_t* codes_dev,
-                              float* hidden_dev, hipStream_t st, int max_row = 0) {
+                              float* hidden_dev, hipStream_t st, int max_row = 0, bool row_positions = false) {
     upload_call_state(t, *sp, rt, max_row > 0 ? max_row : max_new_tokens, suppress_host, n_suppress, st);
+    if (row_positions) {          // every row starts at the prefill's position (the first sample_finish makes T0 - 1 the T0 of a running row)
+        std::vector<int> len0(t->B, t->T0 - 1);
+        copy_on_stream(t->row_len_p, len0.data(), (size_t)t->B * 4, hipMemcpyHostToDevice, st);
+        t->row_pos = true; t->ss.row_len = t->row_len_p; t->max_row_len = 0;
+    }
     auto& g = t->sg;
     g = qtts_talker::StreamGen{};
     g.sp = *sp; g.eos = eos_token_id; g.min_new = min_new_tokens; g.max_new = max_new_tokens;
@@ -1638,12 +1690,16 @@ static void stream_begin_body(qtts_talker* t, const qtts_sampling* sp, const Row
     if (max_row > 0) {
         g.admitting = true; g.max_row = max_row; g.tab = rt->tab;
         g.max_new = t->cfg.max_seq; g.max_frames = std::max(1, max_row - 1); g.total = t->cfg.max_seq - t->T0 - 1;
+        // per-row positions: rows restart at their own prompt's length, so neither the step count nor the positions bound the stream --
+        // its stop latch is "no row unfinished" alone
+        if (row_positions) g.max_new = g.total = 0x3fffffff;
     }
     t->admit_calls = 0; t->admitted_rows = 0;
     t->frames_run = 0;
     t->sample_talker(*sp, eos_token_id, min_new_tokens, max_new_tokens, st);      // token 0
     QTTS_CHECK_HIP(hipMemcpyAsync(&g.done, t->ss.done, 4, hipMemcpyDeviceToHost, st));
     QTTS_CHECK_HIP(hipStreamSynchronize(st));
+    if (t->row_pos) t->mirror_rows(st);
     // the cached frame graph is reusable only when everything it baked in is unchanged (as in qtts_talker_generate)
     const qtts_talker::GraphKey key = t->make_key(*sp, g.eos, g.min_new, g.max_new, g.max_frames, codes_dev, hidden_dev);
     if (!t->cfg.use_graph || !t->any_graph() || !(key == t->graph_key)) { t->destroy_graph(); t->graph_nodes = 0; }
@@ -1680,10 +1736,9 @@ int qtts_talker_stream_begin_rows(qtts_talker* t, const qtts_row_sampling* rows_
     QTTS_API_END
 }
 
-int qtts_talker_stream_begin_admitting(qtts_talker* t, const qtts_row_sampling* rows_host, int32_t n_rows, int32_t max_row_tokens,
-                                       int32_t eos_token_id, const int32_t* suppress_host, int32_t n_suppress, int64_t* codes_dev,
-                                       float* hidden_dev, void* stream) {
-    QTTS_API_BEGIN
+static void begin_admitting_body(qtts_talker* t, const qtts_row_sampling* rows_host, int32_t n_rows, int32_t max_row_tokens, int32_t eos_token_id,
+                                 const int32_t* suppress_host, int32_t n_suppress, int64_t* codes_dev, float* hidden_dev, void* stream,
+                                 bool row_positions) {
     QTTS_REQUIRE(t && rows_host && codes_dev, QTTS_ERR_ARG, "null argument");
     QTTS_REQUIRE(t->prefilled, QTTS_ERR_STATE, "stream_begin_admitting: prefill() first");
     QTTS_REQUIRE(!t->profile, QTTS_ERR_STATE, "stream_begin_admitting: not available in profile mode");
@@ -1696,7 +1751,39 @@ int qtts_talker_stream_begin_admitting(qtts_talker* t, const qtts_row_sampling* 
                                             ") exceeds max_row_tokens (" + std::to_string(max_row_tokens) + ")");
     const qtts_sampling none{};
     stream_begin_body(t, &none, &rt, rt.max_new, rt.poll_from, eos_token_id, suppress_host, n_suppress, codes_dev, hidden_dev, (hipStream_t)stream,
-                      max_row_tokens);
+                      max_row_tokens, row_positions);
+}
+
+int qtts_talker_stream_begin_admitting(qtts_talker* t, const qtts_row_sampling* rows_host, int32_t n_rows, int32_t max_row_tokens,
+                                       int32_t eos_token_id, const int32_t* suppress_host, int32_t n_suppress, int64_t* codes_dev,
+                                       float* hidden_dev, void* stream) {
+    QTTS_API_BEGIN
+    begin_admitting_body(t, rows_host, n_rows, max_row_tokens, eos_token_id, suppress_host, n_suppress, codes_dev, hidden_dev, stream, false);
+    QTTS_API_END
+}
+
+int qtts_talker_stream_begin_admitting_rows(qtts_talker* t, const qtts_row_sampling* rows_host, int32_t n_rows, int32_t max_row_tokens,
+                                            int32_t eos_token_id, const int32_t* suppress_host, int32_t n_suppress, int64_t* codes_dev,
+                                            float* hidden_dev, void* stream) {
+    QTTS_API_BEGIN
+    begin_admitting_body(t, rows_host, n_rows, max_row_tokens, eos_token_id, suppress_host, n_suppress, codes_dev, hidden_dev, stream, true);
+    QTTS_API_END
+}
+
+int qtts_talker_stream_mode(qtts_talker* t, int32_t* row_positions_host, int32_t* max_row_len_host) {
+    QTTS_API_BEGIN
+    QTTS_REQUIRE(t && row_positions_host && max_row_len_host, QTTS_ERR_ARG, "null argument");
+    *row_positions_host = t->row_pos ? 1 : 0;
+    *max_row_len_host = t->row_pos ? t->max_row_len : 0;
+    QTTS_API_END
+}
+
+int qtts_talker_stream_row_lens(qtts_talker* t, int32_t* lens_host) {
+    QTTS_API_BEGIN
+    QTTS_REQUIRE(t && lens_host, QTTS_ERR_ARG, "null argument");
+    QTTS_REQUIRE(t->sg.active && t->row_pos, QTTS_ERR_STATE, "stream_row_lens: no stream with per-row positions is open (qtts_talker_stream_begin_admitting_rows first)");
+    t->mirror_rows(t->sg.st);
+    for (int b = 0; b < t->B; ++b) lens_host[b] = t->row_len_h[b];
     QTTS_API_END
 }
 
@@ -1732,6 +1819,7 @@ int qtts_talker_stream_rows(qtts_talker* t, int32_t* unfinished_host, int32_t* f
         frames_host[b] = e < n_row ? e : std::min(std::max(0, n_row - 1), g.max_frames);
     }
     *kv_len_host = fin[2];
+    if (t->row_pos) { t->mirror_rows(g.st); *kv_len_host = t->longest_row(); }
     QTTS_API_END
 }
 

@@ -311,13 +311,14 @@ class Qwen3TTSForConditionalGeneration:
         # seed of its own: a seed sequence is per request and is only sliced; ONE integer s gives request i of the call s + i,
         # whichever wave it lands in; no seed at all leaves every row to draw a fresh one (`TalkerEngine._row_table`).
         schedule = kwargs.get("schedule", "waves")
-        if schedule not in ("waves", "refill"):
-            raise ValueError(f"`schedule` must be 'waves' or 'refill', but is {schedule!r}")
-        if schedule == "refill":
-            # the whole request list goes to the engine, which admits queued requests into rows as they finish (`TalkerEngine.generate`)
+        if schedule not in ("waves", "refill", "continuous"):
+            raise ValueError(f"`schedule` must be 'waves', 'refill' or 'continuous', but is {schedule!r}")
+        if schedule != "waves":
+            # the whole request list goes to the engine, which admits queued requests into rows as they finish (`TalkerEngine.generate`;
+            # "continuous": on one stream with per-row positions)
             out = self.talker.generate(embeds, mask, trailing, pad, min_new_tokens=2,
                                        eos_token_id=eos_token_id if eos_token_id is not None else c.codec_eos_token_id,
-                                       suppress_tokens=suppress, seed=seed, schedule="refill", **knobs)
+                                       suppress_tokens=suppress, seed=seed, schedule=schedule, **knobs)
             return self._trim_at_eos(out, codes_all, hidden_all)
         per_request = any(_is_row_seq(v) for v in knobs.values()) or _is_row_seq(seed)
         if per_request:
@@ -361,11 +362,12 @@ class Qwen3TTSForConditionalGeneration:
 
         `schedule="refill"`: any number of requests; the talker admits queued requests into rows as they finish and the generator
         yields its `RefillPacket` records unchanged (`TalkerEngine.generate_stream`): per row the request index, the new frames (already
-        cut at eos), and whether the request started or finished with the packet."""
+        cut at eos), and whether the request started or finished with the packet.  `schedule="continuous"`: the same records from one
+        stream with per-row positions."""
         c = self.config
         schedule = kwargs.get("schedule", "waves")
-        if schedule not in ("waves", "refill"):
-            raise ValueError(f"`schedule` must be 'waves' or 'refill', but is {schedule!r}")
+        if schedule not in ("waves", "refill", "continuous"):
+            raise ValueError(f"`schedule` must be 'waves', 'refill' or 'continuous', but is {schedule!r}")
         if schedule == "waves" and len(input_ids) > self.talker.max_batch:
             raise ValueError(f"generate_stream: {len(input_ids)} requests exceed max_batch {self.talker.max_batch}")
         embeds, mask, trailing, pad = self.assemble_prompts(input_ids, languages, speakers, instruct_ids,
@@ -380,7 +382,7 @@ class Qwen3TTSForConditionalGeneration:
                                                   subtalker_temperature=subtalker_temperature, eos_token_id=eos,
                                                   repetition_penalty=repetition_penalty, suppress_tokens=suppress,
                                                   seed=kwargs.get("seed"), schedule=schedule):
-            if schedule == "refill":
+            if schedule != "waves":
                 yield packet
                 continue
             yield split_packet_at_eos(packet, alive, eos)
@@ -716,7 +718,8 @@ class Qwen3TTSModel:
         packet in which it gained no frame, and once it has finished.  Every talker row owns a slot of the codec's state-carrying
         decoder (`CodecDecoderEngine.stream_push_rows`), which decodes only the new frames of a packet; `left_context_size` is NOT
         used under this schedule, and a request's concatenated audio equals the whole-sequence `forward` of its codes, not the
-        chunked rule.  The codec must have been built with a `max_batch` of at least the talker's."""
+        chunked rule.  The codec must have been built with a `max_batch` of at least the talker's.  `schedule="continuous"`: the same
+        on the talker's stream with per-row positions (the codec slots are keyed by row either way)."""
         if self.model.tts_model_type != "custom_voice":
             raise self._unsupported("stream_custom_voice")
         texts = self._ensure_list(text)
@@ -739,10 +742,10 @@ class Qwen3TTSModel:
             gen_kwargs["schedule"] = schedule
         dec = self.model.speech_tokenizer.model.decoder
         cb = dec.config.codebook_size
-        if schedule == "refill":
+        if schedule in ("refill", "continuous"):
             rows = self.model.talker.max_batch
             if dec.max_batch < rows:
-                raise ValueError(f"stream_custom_voice(schedule='refill'): the codec decoder's max_batch ({dec.max_batch}) is smaller than "
+                raise ValueError(f"stream_custom_voice(schedule={schedule!r}): the codec decoder's max_batch ({dec.max_batch}) is smaller than "
                                  f"the talker's ({rows}); every talker row needs a slot of the codec stream")
             sr = int(self.model.speech_tokenizer.model.output_sample_rate)
             dec.stream_begin(rows)

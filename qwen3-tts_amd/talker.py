@@ -190,7 +190,12 @@ class TalkerEngine:
     def stats(self) -> dict:
         st = _lib.TalkerStatsC()
         _lib.check(self._lib.qtts_talker_get_stats(self._h, C.byref(st)))
-        return {f[0]: getattr(st, f[0]) for f in st._fields_}
+        out = {f[0]: getattr(st, f[0]) for f in st._fields_}
+        # (`qtts_talker_stats` keeps its layout under ABI 15: the per-row-position mode's two figures come from a call of their own)
+        rp, longest = C.c_int32(0), C.c_int32(0)
+        _lib.check(self._lib.qtts_talker_stream_mode(self._h, C.byref(rp), C.byref(longest)))
+        out["row_positions"], out["max_row_len"] = int(rp.value), int(longest.value)
+        return out
 
     # ------------------------------------------------------------------ text_projection (prompt assembly)
     @_lib.locked
@@ -315,10 +320,10 @@ class TalkerEngine:
         (`generate_stream` cannot do that after it has yielded packets: there the error reaches the caller, whose retry runs on the
         separate launches.)"""
         schedule = kw.pop("schedule", "waves")
-        if schedule == "refill":
-            return self._generate_refill(*args, **kw)
+        if schedule in ("refill", "continuous"):
+            return self._generate_refill(*args, row_positions=schedule == "continuous", **kw)
         if schedule != "waves":
-            raise ValueError(f"`schedule` must be 'waves' or 'refill', but is {schedule!r}")
+            raise ValueError(f"`schedule` must be 'waves', 'refill' or 'continuous', but is {schedule!r}")
         giveups = self.stats()["cp_fused_giveups"]
         try:
             return self._generate_once(*args, **kw)
@@ -471,17 +476,18 @@ class TalkerEngine:
         `schedule="refill"`: any number of requests on `max_batch` rows, scheduled as `generate(schedule="refill")` schedules them (same
         admission rule, per-row table and seed rules: `_refill_stream`); yields one `RefillPacket` per packet of the running stream
         instead of a block of codes.  Concatenating a request's packets gives exactly the codes `generate(schedule="refill")` returns
-        for it."""
-        if schedule == "refill":
+        for it.  `schedule="continuous"`: the same on ONE stream with per-row positions (`_refill_stream(row_positions=True)`)."""
+        if schedule in ("refill", "continuous"):
             yield from self._refill_stream(inputs_embeds, attention_mask, trailing_text_hidden, tts_pad_embed, packet_frames=packet_frames,
                                            max_new_tokens=max_new_tokens, min_new_tokens=min_new_tokens, do_sample=do_sample, top_k=top_k,
                                            top_p=top_p, temperature=temperature, subtalker_dosample=subtalker_dosample,
                                            subtalker_top_k=subtalker_top_k, subtalker_top_p=subtalker_top_p,
                                            subtalker_temperature=subtalker_temperature, eos_token_id=eos_token_id,
-                                           repetition_penalty=repetition_penalty, suppress_tokens=suppress_tokens, seed=seed)
+                                           repetition_penalty=repetition_penalty, suppress_tokens=suppress_tokens, seed=seed,
+                                           row_positions=schedule == "continuous")
             return
         if schedule != "waves":
-            raise ValueError(f"`schedule` must be 'waves' or 'refill', but is {schedule!r}")
+            raise ValueError(f"`schedule` must be 'waves', 'refill' or 'continuous', but is {schedule!r}")
         c = self.config
         if inputs_embeds.dim() != 3 or inputs_embeds.shape[-1] != c.hidden_size:
             raise ValueError(f"inputs_embeds must be (B, T, {c.hidden_size})")
@@ -562,10 +568,13 @@ class TalkerEngine:
     # ------------------------------------------------------------------ admission into finished rows (include/qtts.h, ABI v15)
     @_lib.locked
     def stream_open(self, inputs_embeds: torch.Tensor, n_pad: List[int], trailing_text_hidden: torch.Tensor, tts_pad_embed: torch.Tensor,
-                    rows, max_row_tokens: int, eos_token_id: int, suppress_tokens: List[int], output_hidden_states: bool = False):
+                    rows, max_row_tokens: int, eos_token_id: int, suppress_tokens: List[int], output_hidden_states: bool = False,
+                    row_positions: bool = False):
         """Prefill + `qtts_talker_stream_begin_admitting`: `rows` is a `_lib.RowSamplingC` array with one entry per row of
         `inputs_embeds` (B, T, H; row b left-padded by n_pad[b]).  Returns (codes (B, max_row_tokens - 1, G), hidden or None): the
-        blocks the stream fills, ONE occupant per row at a time -- copy a finished row out before `stream_admit` re-uses it."""
+        blocks the stream fills, ONE occupant per row at a time -- copy a finished row out before `stream_admit` re-uses it.
+        `row_positions=True` opens the stream with `qtts_talker_stream_begin_admitting_rows`: every row carries its own KV length, an
+        admitted prompt restarts its row at its own length, and `stream_row_lens()` reads the lengths back."""
         c, dev = self.config, self.device
         B, T, H = inputs_embeds.shape
         if B > self.max_batch:
@@ -583,7 +592,8 @@ class TalkerEngine:
         with torch.cuda.device(dev), torch.cuda.stream(self._stream):
             _lib.check(self._lib.qtts_talker_prefill(self._h, C.c_void_p(emb.data_ptr()), B, T, npad_c, C.c_void_p(trail.data_ptr()),
                                                      trail.shape[1], C.c_void_p(pad.data_ptr()), self._s()))
-            _lib.check(self._lib.qtts_talker_stream_begin_admitting(
+            begin = self._lib.qtts_talker_stream_begin_admitting_rows if row_positions else self._lib.qtts_talker_stream_begin_admitting
+            _lib.check(begin(
                 self._h, rows, B, int(max_row_tokens), int(eos_token_id), sup_c, len(suppress_tokens), C.c_void_p(codes.data_ptr()),
                 C.c_void_p(hidden.data_ptr()) if hidden is not None else None, self._s()))
         self._open = (codes, hidden)          # (the stream writes these blocks until `stream_close`)
@@ -614,6 +624,15 @@ class TalkerEngine:
         return list(uf), list(fr), int(kv.value)
 
     @_lib.locked
+    def stream_row_lens(self) -> List[int]:
+        """`qtts_talker_stream_row_lens`: every row's KV length on a stream opened with `row_positions=True` (a finished row: the length
+        it froze at)."""
+        lens = (C.c_int32 * self._live_batch)()
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.qtts_talker_stream_row_lens(self._h, lens))
+        return list(lens)
+
+    @_lib.locked
     def stream_step(self, max_frames_now: int):
         """`qtts_talker_stream_step` on the open stream: (frame steps the stream has run, whether its stop condition has latched)."""
         total, fin = C.c_int32(0), C.c_int32(0)
@@ -637,7 +656,7 @@ class TalkerEngine:
                        tts_pad_embed: torch.Tensor, max_new_tokens=2048, min_new_tokens=2, do_sample=True, top_k=50, top_p=1.0,
                        temperature=0.9, subtalker_dosample=True, subtalker_top_k=50, subtalker_top_p=1.0, subtalker_temperature=0.9,
                        eos_token_id: Optional[int] = None, repetition_penalty=1.05, suppress_tokens: Optional[List[int]] = None,
-                       output_hidden_states: bool = False, seed=None, packet_frames: int = 4, **unused):
+                       output_hidden_states: bool = False, seed=None, packet_frames: int = 4, row_positions: bool = False, **unused):
         """The refill schedule, packet by packet (`generate_stream(..., schedule="refill")`; `generate(..., schedule="refill")` collects
         what this yields): any number of requests on `max_batch` rows.  The rows start with the requests of the longest prompts; the
         stream runs in packets of `packet_frames` frames; after each packet every row whose occupant gained frames or finished is
@@ -647,7 +666,13 @@ class TalkerEngine:
         row has finished, the stream ends and a fresh one begins with the remainder.  Always runs on the per-row table (scalars are
         broadcast; seeds as in `_row_table`: a list is per request, one integer s gives request i the seed s + i, none draws fresh
         ones), so a request's codes do not depend on when or where it was admitted.  Closing the generator closes the stream;
-        `last_refill` is filled either way.  Holds the engine lock while active."""
+        `last_refill` is filled either way.  Holds the engine lock while active.
+
+        `row_positions=True` (`schedule="continuous"`): the stream carries per-row positions, so the fit test on the position is gone --
+        after every packet every queued request for which a row is free is admitted, in queue order (a group whose padded length would
+        push one of its members past max_seq is split into several `stream_admit` calls) -- and ONE stream serves the whole call, at
+        full width: the opening group is the widest that fits (`_widest_opener`) and the remaining rows start as spare rows.
+        `last_refill["max_row_len"]` is the largest row length seen."""
         c, dev = self.config, self.device
         if inputs_embeds.dim() != 3 or inputs_embeds.shape[-1] != c.hidden_size:
             raise ValueError(f"inputs_embeds must be (B, T, {c.hidden_size})")
@@ -680,7 +705,20 @@ class TalkerEngine:
         mb = self.max_batch
         max_row = max(int(rows[i].max_new_tokens) for i in range(N))
         queue = sorted(range(N), key=lambda i: (-lens[i], i))
-        st = dict(streams=0, admit_calls=0, admitted_rows=0, frames_run=0, row_frames=0, graph_captures=0)
+        st = dict(streams=0, admit_calls=0, admitted_rows=0, frames_run=0, row_frames=0, graph_captures=0, max_row_len=0)
+        limit = lambda i: int(rows[i].max_new_tokens)
+
+        def admission_groups(idx):
+            """per-row positions: `idx` in queue order, cut into groups in each of which the padded length + every limit fits max_seq"""
+            groups = []
+            for i in idx:
+                cand = (groups[-1] if groups else []) + [i]
+                Tg = max(lens[j] for j in cand)
+                if groups and all(Tg + limit(j) <= self.max_seq for j in cand):
+                    groups[-1] = cand
+                else:
+                    groups.append([i])
+            return groups
 
         def group(idx):
             Tg = max(lens[i] for i in idx)
@@ -694,11 +732,20 @@ class TalkerEngine:
                     # a fresh stream: the longest prompt first, then the longest of the rest whose limits fit behind it
                     T0 = lens[queue[0]]
                     first = [i for i in queue if T0 + int(rows[i].max_new_tokens) <= self.max_seq][:mb]
+                    spare = 0
+                    if row_positions:
+                        # the ONE stream's width is its opening group's (an admission takes a row of the stream): open with the widest
+                        # group that fits, and bring the stream to full width with spare rows -- copies of the first prompt under the
+                        # limit 1, finished with their token 0 -- that the first admission fills
+                        first = self._widest_opener(queue, lens, [limit(i) for i in range(N)], self.max_seq, mb)
+                        spare = min(mb, N) - len(first)
                     queue = [i for i in queue if i not in first]
-                    e, npd, tr, tab = group(first)
-                    codes, hidden = self.stream_open(e, npd, tr, pad, tab, max_row, eos, suppress_tokens, output_hidden_states)
+                    e, npd, tr, tab = group(first + first[:1] * spare)
+                    for k in range(len(first), len(first) + spare):
+                        tab[k].max_new_tokens, tab[k].min_new_tokens = 1, 0
+                    codes, hidden = self.stream_open(e, npd, tr, pad, tab, max_row, eos, suppress_tokens, output_hidden_states, row_positions)
                     st["streams"] += 1
-                    slot, seen, fresh = list(first), [0] * len(first), set(first)
+                    slot, seen, fresh = list(first) + [None] * spare, [0] * (len(first) + spare), set(first)
                     try:
                         while any(r is not None for r in slot):
                             self.stream_step(packet_frames)
@@ -718,10 +765,19 @@ class TalkerEngine:
                                     slot[b] = None
                             yield RefillPacket(packet)
                             free = [b for b, r in enumerate(slot) if r is None]
-                            take = [i for i in queue if lens[i] <= kv_len and kv_len + int(rows[i].max_new_tokens) <= self.max_seq][:len(free)]
+                            if row_positions:
+                                take = queue[:len(free)]
+                                at = 0
+                                for grp in admission_groups(take):
+                                    e, npd, tr, tab = group(grp)
+                                    self.stream_admit(free[at:at + len(grp)], e, npd, tr, tab)
+                                    at += len(grp)
+                            else:
+                                take = [i for i in queue if lens[i] <= kv_len and kv_len + limit(i) <= self.max_seq][:len(free)]
+                                if take:
+                                    e, npd, tr, tab = group(take)
+                                    self.stream_admit(free[:len(take)], e, npd, tr, tab)
                             if take:
-                                e, npd, tr, tab = group(take)
-                                self.stream_admit(free[:len(take)], e, npd, tr, tab)
                                 for b, r in zip(free, take):
                                     slot[b], seen[b] = r, 0
                                     fresh.add(r)
@@ -730,17 +786,32 @@ class TalkerEngine:
                         s1 = self.stats()
                         st["admit_calls"] += s1["admit_calls"]
                         st["admitted_rows"] += s1["admitted_rows"]
+                        st["max_row_len"] = max(st["max_row_len"], s1["max_row_len"]) if row_positions else 0
                         st["frames_run"] += self.stream_close()
             finally:
                 st["graph_captures"] = self.stats()["graph_captures"] - caps0
                 st["occupancy"] = st["row_frames"] / max(1, st["frames_run"] * mb)
                 self.last_refill = st
 
+    @staticmethod
+    def _widest_opener(queue, lens, limits, max_seq, max_batch):
+        """The opening group of a stream with per-row positions: among the groups {requests no longer than T whose limit fits behind T}
+        for every prompt length T, the one with the most members (at most max_batch, longest prompts first; ties go to the longer T).
+        `queue` is sorted longest first.  Limits clamped to the room their own prompt leaves (`_clamp_new_tokens`) fit only behind
+        their own length, so the group can be narrow: the scheduler fills the stream's other rows with spare rows."""
+        best = []
+        for T in sorted({lens[i] for i in queue}, reverse=True):
+            cand = [i for i in queue if lens[i] <= T and T + limits[i] <= max_seq][:max_batch]
+            if len(cand) > len(best):
+                best = cand
+        return best
+
     def _generate_refill(self, inputs_embeds: torch.Tensor, attention_mask: torch.Tensor, trailing_text_hidden: torch.Tensor,
                          tts_pad_embed: torch.Tensor, max_new_tokens=2048, min_new_tokens=2, do_sample=True, top_k=50, top_p=1.0,
                          temperature=0.9, subtalker_dosample=True, subtalker_top_k=50, subtalker_top_p=1.0, subtalker_temperature=0.9,
                          eos_token_id: Optional[int] = None, repetition_penalty=1.05, suppress_tokens: Optional[List[int]] = None,
-                         output_hidden_states: bool = True, seed=None, packet_frames: int = 4, **unused) -> TalkerGenerateOutput:
+                         output_hidden_states: bool = True, seed=None, packet_frames: int = 4, row_positions: bool = False,
+                         **unused) -> TalkerGenerateOutput:
         """`generate(..., schedule="refill")`: the packets of `_refill_stream` (its arguments and schedule) collected per request.
         Returns the requests in the order given, in `generate`'s structure: codes (N, F, G) with eos in codebook 0 behind a request's
         last frame, tokens (N, F + 1)."""
@@ -753,7 +824,8 @@ class TalkerEngine:
                                           temperature=temperature, subtalker_dosample=subtalker_dosample, subtalker_top_k=subtalker_top_k,
                                           subtalker_top_p=subtalker_top_p, subtalker_temperature=subtalker_temperature, eos_token_id=eos,
                                           repetition_penalty=repetition_penalty, suppress_tokens=suppress_tokens,
-                                          output_hidden_states=output_hidden_states, seed=seed, packet_frames=packet_frames):
+                                          output_hidden_states=output_hidden_states, seed=seed, packet_frames=packet_frames,
+                                          row_positions=row_positions):
             for e in packet.rows:
                 parts[e.request].append(e.codes)
                 hparts[e.request].append(e.hidden)

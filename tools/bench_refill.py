@@ -1,16 +1,17 @@
 #!/usr/bin/env python3
-"""Static waves against the refill schedule on a ragged request list: 1.7B dims, bf16, captured frame graph, sampling with EOS blocked
-and a per-request `max_new_tokens`, 4 x `max_batch` requests, both schedules in ONE process on one engine per batch size.
+"""Static waves against the refill and the continuous schedule on a ragged request list: 1.7B dims, bf16, captured frame graph, sampling
+with EOS blocked and a per-request `max_new_tokens`, 4 x `max_batch` requests, all schedules in ONE process on one engine per batch size.
 
     python tools/bench_refill.py                      # max_batch 8 and 32
     python tools/bench_refill.py --batch 8 --rounds 2 --scale 0.5
 
 The length list is fixed (no random source): request i asks for `scale` x LENGTHS[i % 16] tokens, lengths an order of magnitude apart as
 utterances are.  `waves` is `TalkerEngine.generate` on slices of `max_batch` requests in the order given (what
-`Qwen3TTSForConditionalGeneration.generate` does), `refill` is `generate(schedule="refill")` on the whole list.  One JSON line per
-batch size: wall seconds of every round and the minimum per schedule, frame steps run, and the row occupancy each schedule achieved
-(useful row-frames / (frame steps x max_batch)).  Process-to-process variance on shared machines is a few per cent; the two schedules
-of one line ran interleaved in the same process."""
+`Qwen3TTSForConditionalGeneration.generate` does), `refill` is `generate(schedule="refill")` on the whole list (one shared position per
+stream), `continuous` is `generate(schedule="continuous")` (per-row positions: one stream, every row attends over its own occupant's
+keys).  One JSON line per batch size: wall seconds of every round and the minimum per schedule, frame steps run, milliseconds per frame
+step (prefills and admissions included) and the row occupancy each schedule achieved (useful row-frames / (frame steps x max_batch)).
+Process-to-process variance on shared machines is a few per cent; the schedules of one line ran interleaved in the same process."""
 import argparse
 import json
 import os
@@ -64,24 +65,34 @@ def main():
             eng.generate(*args, schedule="refill", max_new_tokens=limits, packet_frames=a.packet, **kw)
             return eng.last_refill["frames_run"]
 
-        res = {"waves": [], "refill": []}
-        steps = {}
-        for fn in (waves, refill):          # warm-up: captures, allocator
-            fn()
+        def continuous():
+            eng.generate(*args, schedule="continuous", max_new_tokens=limits, packet_frames=a.packet, **kw)
+            return eng.last_refill["frames_run"]
+
+        names = ("waves", "refill", "continuous")
+        fns = dict(waves=waves, refill=refill, continuous=continuous)
+        res = {n: [] for n in names}
+        steps, sched = {}, {}
+        for n in names:                     # warm-up: captures, allocator
+            fns[n]()
         for _ in range(a.rounds):
-            for name, fn in (("waves", waves), ("refill", refill)):
+            for name, fn in fns.items():
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
                 steps[name] = fn()
                 torch.cuda.synchronize()
                 res[name].append(round(time.perf_counter() - t0, 4))
+                if name != "waves":
+                    sched[name] = dict(eng.last_refill)
         line = {"bench": "refill", "max_batch": B, "requests": N, "layers": a.layers, "useful_row_frames": useful, "max_seq": max_seq,
                 "packet_frames": a.packet}
-        for name in ("waves", "refill"):
+        for name in names:
             line[name] = {"seconds": res[name], "min_seconds": min(res[name]), "frame_steps": steps[name],
-                          "occupancy": round(useful / (steps[name] * B), 3)}
-        line["refill"].update({k: eng.last_refill[k] for k in ("streams", "admit_calls", "admitted_rows")})
+                          "ms_per_frame": round(1e3 * min(res[name]) / steps[name], 4), "occupancy": round(useful / (steps[name] * B), 3)}
+        for name in ("refill", "continuous"):
+            line[name].update({k: sched[name][k] for k in ("streams", "admit_calls", "admitted_rows", "max_row_len", "graph_captures")})
         line["speedup"] = round(line["waves"]["min_seconds"] / line["refill"]["min_seconds"], 3)
+        line["speedup_continuous"] = round(line["waves"]["min_seconds"] / line["continuous"]["min_seconds"], 3)
         print(json.dumps(line), flush=True)
 
 
