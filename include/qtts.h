@@ -314,7 +314,9 @@ typedef struct {
     /* max_batch: sequences per generate call, 1..64 (QTTS_ERR_LIMIT outside).  A call may bring any smaller batch; the frame step's
        launches follow the batch of the call.  The KV pools are reserved for max_batch x max_seq at finalize: at max_batch 64, max_seq
        4096, 1.7B dims (28 layers x 8 kv heads x 128) in bf16 that is 64 x 4096 x 28 x 2 x 8 x 128 x 2 B = 30.1 GB for the talker (plus
-       42 MB for the code predictor) -- max_seq is the lever: 1024 keeps it at 7.5 GB.  Decode scratch above 32 rows grows by the code
+       42 MB for the code predictor) -- max_seq is one lever: 1024 keeps it at 7.5 GB.  The other is a shared page pool
+       (qtts_talker_set_kv_pool below): the talker cache then holds n_pages pages of 16 keys (1.835 MB each at these dims; the 30.1 GB
+       are 16 384 pages) that the rows take as they grow, and max_seq only bounds one request.  Decode scratch above 32 rows grows by the code
        predictor's two-token first pass only (2 x max_batch rows).  QTTS_SKINNY_WIDE=0 (qtts_set_option; A/B runs) sends that pass's
        65..128-row GEMMs out as two launches of <= 64 rows instead of one. */
     int32_t max_batch;
@@ -512,8 +514,43 @@ int qtts_talker_stream_row_lens(qtts_talker* t, int32_t* lens_host /* (B) */);
  * have a call of their own. */
 int qtts_talker_stream_mode(qtts_talker* t, int32_t* row_positions_host, int32_t* max_row_len_host);
 
+/* Shared KV page pool for the talker cache (entry points added under ABI 15; no struct changed).
+ *   set_kv_pool   between create and finalize (QTTS_ERR_STATE afterwards).  finalize then allocates n_pages + 1 pages of 16 keys for the
+ *                 talker's K and V pools instead of max_batch x ceil(max_seq / 16); the extra page is a SINK.  n_pages = 0: the static
+ *                 layout (the default).  0 < n_pages < ceil(max_seq / 16) is refused with QTTS_ERR_LIMIT: one request of max_seq keys
+ *                 must always fit.  The code predictor's cache stays static.  The choice lives in the handle.
+ *   Table invariant: every entry of the page table names a valid page at all times; an entry without a grant names the sink, which is
+ *                 zero-filled at finalize.  Speculative loads beyond a row's length and the appends of a finished row at its frozen
+ *                 length therefore land in memory nobody reads unmasked.  The allocator is a host-side free list in the engine (last
+ *                 released, first granted: deterministic); the table lives in device memory and only the entries that changed are
+ *                 patched, on the stream, between frame-graph launches (a grant captures no graph).
+ *   Streams with per-row positions take pages as they grow: prefill and stream_admit grant a row ceil(T / 16) pages for the group's
+ *                 padded T (stream_admit: QTTS_ERR_LIMIT when the group's prompt pages do not fit, nothing changed);
+ *                 stream_step(max_frames_now) first makes sure every running row holds the pages of
+ *                 len + min(max_frames_now, frames left under its limit) keys, and is refused with QTTS_ERR_LIMIT -- the message gives the
+ *                 pages needed and the pages free -- when the pool cannot cover that: no row advanced, no page moved.  A row's pages
+ *                 go back to the pool at the first stream_step / stream_rows return that observes it finished (copy frames out of
+ *                 codes_dev, never out of the cache).
+ *   Every other path reserves its worst case when it begins -- generate, generate_rows, stream_begin, stream_begin_rows:
+ *                 B x ceil((T + max_new_tokens) / 16) pages; the shared-position admitting stream: whole rows -- and is refused with
+ *                 QTTS_ERR_LIMIT (the prefill stays valid) when that does not fit.  Results on a pooled engine are the static engine's.
+ *   stream_kv     pages_host[b] = pages row b holds (b < the batch of the last prefill), the free pages, the pool size.
+ *                 QTTS_ERR_STATE on an engine without a pool.
+ *   stream_evict  on a stream with per-row positions: the listed rows' occupants are abandoned -- the rows are marked finished on the
+ *                 device, their lengths freeze where stream_row_lens reports them, their pages go back to the pool.  This is preemption
+ *                 by restart (a request's codes depend on its seed and its own step only: admitted again it produces the same codes)
+ *                 and the way to cancel a request; on an engine without a pool it frees nothing.  Rows listed twice or out of range:
+ *                 QTTS_ERR_ARG, nothing changed. */
+int qtts_talker_set_kv_pool(qtts_talker* t, int32_t n_pages);
+int qtts_talker_stream_kv(qtts_talker* t, int32_t* pages_host /* (B) */, int32_t* free_host, int32_t* pool_host);
+int qtts_talker_stream_evict(qtts_talker* t, int32_t n, const int32_t* rows_host);
+
 /* Test/diagnostic hooks (device -> caller device buffers, after prefill / a generate call). */
 int qtts_talker_debug_logits(qtts_talker* t, float* logits_dev /* (B, vocab) */, void* stream);
+/* The talker cache's page table of one row (0 <= row < max_batch) as it stands on the DEVICE -- what the next launch on `stream` reads:
+   ceil(max_seq / 16) entries in slot order.  On a pooled engine an entry without a grant holds n_pages (the sink); on a static engine
+   entry i of row b is b x ceil(max_seq / 16) + i.  Synchronises `stream`. */
+int qtts_talker_debug_kv_table(qtts_talker* t, int32_t row, int32_t* entries_host /* (ceil(max_seq / 16)) */, void* stream);
 /* The code predictor's RAW logits of the last frame step that ran, every pass: what `code_predictor.generate`'s lm_head[j] returned
  * before HF's processors (modeling_qwen3_tts.py:1250-1312; the sampled path is checked against the processed softmax of exactly
  * these numbers, tests/test_gpu_parity.py).  The frame step keeps one row block per pass, so nothing is added to it.  ABI v11. */

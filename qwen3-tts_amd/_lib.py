@@ -110,7 +110,8 @@ SYMBOLS = ["qtts_last_error", "qtts_abi_version", "qtts_set_option", "qtts_get_o
            "qtts_talker_generate_rows", "qtts_talker_stream_begin_rows",
            "qtts_talker_stream_begin_admitting", "qtts_talker_stream_admit", "qtts_talker_stream_rows",
            "qtts_talker_stream_begin_admitting_rows", "qtts_talker_stream_row_lens", "qtts_talker_stream_mode",
-           "qtts_talker_debug_logits", "qtts_talker_debug_cp_logits", "qtts_talker_get_stats", "qtts_talker_get_gemm_profile", "qtts_talker_set_teacher",
+           "qtts_talker_set_kv_pool", "qtts_talker_stream_kv", "qtts_talker_stream_evict",
+           "qtts_talker_debug_logits", "qtts_talker_debug_kv_table", "qtts_talker_debug_cp_logits", "qtts_talker_get_stats", "qtts_talker_get_gemm_profile", "qtts_talker_set_teacher",
            "qtts_talker_set_profile"]
 
 
@@ -205,6 +206,10 @@ def load_library():
     lib.qtts_talker_stream_begin_admitting_rows.argtypes = lib.qtts_talker_stream_begin_admitting.argtypes
     lib.qtts_talker_stream_row_lens.argtypes = [vp, C.POINTER(C.c_int32)]
     lib.qtts_talker_stream_mode.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    lib.qtts_talker_set_kv_pool.argtypes = [vp, i32]
+    lib.qtts_talker_stream_kv.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    lib.qtts_talker_stream_evict.argtypes = [vp, i32, C.POINTER(C.c_int32)]
+    lib.qtts_talker_debug_kv_table.argtypes = [vp, i32, C.POINTER(C.c_int32), vp]
     lib.qtts_talker_stream_admit.argtypes = [vp, i32, C.POINTER(C.c_int32), f32p, i32, C.POINTER(C.c_int32), f32p, i32,
                                              C.POINTER(RowSamplingC), vp]
     lib.qtts_talker_stream_rows.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]

@@ -931,10 +931,23 @@ __global__ __launch_bounds__(256) void attn_tk_kernel(AttnDecodeParams p) {
         const int page = CT ? b * p.kv.pages_per_seq + (s >> 4) : p.kv.page_table[b * p.kv.pages_per_seq + (s >> 4)];
         return ((((size_t)p.layer * p.kv.n_pages + page) * p.kv.nkv + kvh) * 16 + (s & 15)) * HD + li * 8;
     };
+    // A shared page pool (CT = false): key g + 16 pg lies in page pg of the row for EVERY lane, so the table index of a chunk's four
+    // pages is wave-uniform (b comes from blockIdx).  Written that way the entries are fetched by scalar loads -- they count on lgkmcnt
+    // and never sit in the K / V request queue -- the kernel waits for them once, and the speculative chunk requests go out back to
+    // back exactly as in the CT form (indexed by the lane's own `s >> 4` every request sat behind a vector load of its page id).  The
+    // address is the one kv_off gives: beyond the row's pages, page pps - 1 at slot 15.
+    auto kv_off_pg = [&](int pg) -> size_t {
+        const bool in = pg < p.kv.pages_per_seq;
+        const int page = p.kv.page_table[b * p.kv.pages_per_seq + (in ? pg : p.kv.pages_per_seq - 1)];
+        return ((((size_t)p.layer * p.kv.n_pages + page) * p.kv.nkv + kvh) * 16 + (in ? g : 15)) * HD + li * 8;
+    };
     auto load_chunk = [&](u32x4 (&r)[CH][KW], const KVT* base, int c) {
 #pragma unroll
         for (int i = 0; i < CH; ++i) {
-            const u32x4* src = reinterpret_cast<const u32x4*>(base + kv_off(g + 16 * (c * CH + i)));
+            size_t off;
+            if constexpr (CT) off = kv_off(g + 16 * (c * CH + i));
+            else off = kv_off_pg(c * CH + i);
+            const u32x4* src = reinterpret_cast<const u32x4*>(base + off);
 #pragma unroll
             for (int w = 0; w < KW; ++w) r[i][w] = src[w];
         }
@@ -1193,10 +1206,10 @@ __global__ __launch_bounds__(256) void attn_tk16_kernel(AttnDecodeParams p) {
 
     // element offset of (page pg of this sequence, this kv head) -- the same for the K pool ([16][128]) and the V pool ([128][16])
     auto page_base = [&](int pg) -> size_t {
-        // speculative READS stay inside the sequence's pages (what they fetch beyond the live length is dropped at use).  With a page
-        // table (CT = false) every entry (b, pg < pps) must therefore be populated at create -- the engine reserves all pages of a
-        // sequence up front.  The APPEND below never goes through the clamp: a step at capacity writes nothing (`fits`), it does not
-        // overwrite the last page (the host refuses such a step first: max_seq check in qtts_talker_generate).
+        // speculative READS stay inside the sequence's table entries (what they fetch beyond the live length is dropped at use).  With a
+        // page table (CT = false) every entry (b, pg < pps) must therefore name a valid page AT ALL TIMES: a page the row was granted, or
+        // -- a shared pool, entries without a grant -- the zero-filled sink page (talker_engine.hip: pool_*; DESIGN.md, table invariant).
+        // The APPEND below never goes through the clamp: a step at capacity writes nothing (`fits`); the host refuses such a step first.
         pg = pg < pps ? pg : pps - 1;
         const int page = CT ? b * pps + pg : p.kv.page_table[b * pps + pg];
         return (((size_t)p.layer * p.kv.n_pages + page) * p.kv.nkv + kvh) * (16 * HD);
@@ -1204,14 +1217,26 @@ __global__ __launch_bounds__(256) void attn_tk16_kernel(AttnDecodeParams p) {
     // K fragments of block `blk`: tile A rows = keys {0-3, 8-11} of both pages, tile B rows = keys {4-7, 12-15}; lane (row lj, lq)
     // holds dims 32 t + 8 lq .. + 8 for k-step t.  V fragments: dim block d (16 dims), lane (dim 16 d + lj, lq) holds keys
     // 8 lq .. 8 lq + 7 of the block = keys 8 (lq & 1) .. + 8 of page 2 blk + (lq >> 1).
+    // A shared page pool (CT = false): a block spans the pages 2 blk and 2 blk + 1 of the row, and which of the two a lane reads depends
+    // on the lane -- but the two table entries do not (blk is wave-uniform, b comes from blockIdx): both are fetched by scalar loads
+    // (lgkmcnt: outside the K / V request queue) and the lane selects between two VALUES, so the block requests go out back to back as in
+    // the CT form.  Same clamp as page_base.
+    auto page_pair = [&](int pg0, bool second) -> size_t {
+        const int i0 = pg0 < pps ? pg0 : pps - 1, i1 = pg0 + 1 < pps ? pg0 + 1 : pps - 1;
+        const int t0 = p.kv.page_table[b * pps + i0], t1 = p.kv.page_table[b * pps + i1];
+        return (((size_t)p.layer * p.kv.n_pages + (second ? t1 : t0)) * p.kv.nkv + kvh) * (16 * HD);
+    };
     auto load_block = [&](u32x4 (&kA)[4], u32x4 (&kB)[4], u32x4 (&vT)[8], int blk) {
-        const size_t pk = page_base(2 * blk + (lj >> 3));                  // rows 0-7: first page, rows 8-15: second page
+        size_t pk, pv;
+        if constexpr (CT) pk = page_base(2 * blk + (lj >> 3));             // rows 0-7: first page, rows 8-15: second page
+        else pk = page_pair(2 * blk, (lj >> 3) != 0);
         const int kin = ((lj >> 2) & 1) * 8 + (lj & 3);                    // key inside the page for tile A (tile B: + 4)
         const u32x4* ka = reinterpret_cast<const u32x4*>(kc + pk + (size_t)kin * HD + lq * 8);
         const u32x4* kb = reinterpret_cast<const u32x4*>(kc + pk + (size_t)(kin + 4) * HD + lq * 8);
 #pragma unroll
         for (int t = 0; t < 4; ++t) { kA[t] = ka[t * 4]; kB[t] = kb[t * 4]; }     // (32 dims = 64 B = 4 x 16-B units per k-step)
-        const size_t pv = page_base(2 * blk + (lq >> 1));
+        if constexpr (CT) pv = page_base(2 * blk + (lq >> 1));
+        else pv = page_pair(2 * blk, (lq >> 1) != 0);
         const u32x4* vb = reinterpret_cast<const u32x4*>(vc + pv + (size_t)lj * 16 + (lq & 1) * 8);
 #pragma unroll
         for (int d = 0; d < 8; ++d) vT[d] = vb[d * 32];                    // (16 dims x 16 keys x 2 B = 512 B = 32 units per dim block)

@@ -9,7 +9,9 @@
 // HBM layout:
 //   weights   decode: packed 1-KiB MFMA tiles (skinny.hip), fp32 or bf16; prefill: row-major [N][K] copy
 //   KV cache  paged, 16 tokens per page: pool[layer][page][kv_head][16][128] (fp32 or bf16), page table per
-//             sequence reserved at create for max_seq tokens (no growth inside the captured step)
+//             sequence reserved at create for max_seq tokens (no growth inside the captured step) -- or, with a shared pool
+//             (qtts_talker_set_kv_pool), pool[layer][n_pages + 1] granted page by page from a host-side free list, the table
+//             patched between graph launches, unallocated entries naming the sink page
 //   state     residual stream / qkv / mlp activations fp32 [rows <= 64][dim]; rows = t*B + b
 #include <atomic>
 #include <map>
@@ -610,6 +612,88 @@ struct qtts_talker {
     // ... and the largest length any of them can reach within `burst` more steps: a finished row's length is frozen, so it keeps no
     // bucket alive, and the bucket goes down again when the long row retires
     int row_reach(int burst) const { return std::min(cfg.max_seq, std::max(1, longest_row() + burst)); }
+    // ---- shared KV page pool (qtts_talker_set_kv_pool; 0 pages: the static layout, every row owns max_seq keys)
+    // The talker's K / V pools hold pool_pages + 1 pages: page `pool_pages` is the SINK.  Every entry of the device table names a valid
+    // page at all times -- a granted one, or the sink -- so the speculative loads beyond a row's length and the appends of a finished row
+    // at its frozen length land in memory that nobody reads unmasked (the sink is zero-filled at finalize and only ever receives keys).
+    // The allocator is this host-side free list (last released, first granted: deterministic); nothing is allocated on the device.
+    // The table lives in device memory and the captured frame graphs read it: `pool_flush` patches the entries that changed, on the
+    // stream, between graph launches.
+    int pool_pages = 0;
+    std::vector<int> pool_free;                  // stack of free page ids (back = next grant)
+    std::vector<std::vector<int>> pool_row;      // pages a row holds, in slot order
+    std::vector<int> ptab_h;                     // host copy of the device table [max_batch][pages_per_seq]
+    std::vector<std::pair<int, int>> pool_dirty; // (first entry, count) runs of ptab_h not yet on the device
+    bool pooled() const { return pool_pages > 0; }
+    int pool_held(int b) const { return (int)pool_row[b].size(); }
+    // row b holds at least `want` pages afterwards (the caller has checked that the free list covers it)
+    void pool_grant(int b, int want) {
+        const int pps = kv_t.pages_per_seq, have = pool_held(b);
+        if (want <= have) return;
+        for (int i = have; i < want; ++i) {
+            const int pg = pool_free.back();
+            pool_free.pop_back();
+            pool_row[b].push_back(pg);
+            ptab_h[(size_t)b * pps + i] = pg;
+        }
+        pool_dirty.emplace_back(b * pps + have, want - have);
+    }
+    void pool_release(int b) {
+        const int pps = kv_t.pages_per_seq, have = pool_held(b);
+        if (!have) return;
+        for (int i = have - 1; i >= 0; --i) { pool_free.push_back(pool_row[b][i]); ptab_h[(size_t)b * pps + i] = pool_pages; }
+        pool_row[b].clear();
+        pool_dirty.emplace_back(b * pps, have);
+    }
+    void pool_flush(hipStream_t st) {
+        if (pool_dirty.empty()) return;
+        for (auto& d : pool_dirty)
+            QTTS_CHECK_HIP(hipMemcpyAsync(ptab_t.as<int>() + d.first, ptab_h.data() + d.first, (size_t)d.second * 4, hipMemcpyHostToDevice, st));
+        QTTS_CHECK_HIP(hipStreamSynchronize(st));      // (ptab_h may change again before the next launch)
+        pool_dirty.clear();
+    }
+    // every row b < n holds `want` pages afterwards, or the call is refused with nothing changed
+    void pool_reserve_rows(int n, int want, const char* who, hipStream_t st) {
+        if (!pooled()) return;
+        int need = 0;
+        for (int b = 0; b < n; ++b) need += std::max(0, want - pool_held(b));
+        if (need > (int)pool_free.size())
+            throw Error(QTTS_ERR_LIMIT, std::string(who) + ": the KV page pool cannot cover the call's worst case (" + std::to_string(need) +
+                                            " pages needed, " + std::to_string(pool_free.size()) + " free of " + std::to_string(pool_pages) + ")");
+        for (int b = 0; b < n; ++b) pool_grant(b, want);
+        pool_flush(st);
+    }
+    // per-row positions: the pages of every row the mirror shows finished go back to the pool
+    void pool_release_finished(hipStream_t st) {
+        if (!pooled() || !row_pos) return;
+        for (int b = 0; b < B; ++b)
+            if (!row_unf_h[b]) pool_release(b);
+        pool_flush(st);
+    }
+    // per-row positions, before `n` more frame steps: every running row holds the pages of len + min(n, the frames left under its limit)
+    // keys (a frame step appends at slot len and a row runs limit - 1 steps), or the call is refused with nothing changed.  Rows the
+    // mirror shows finished give their pages back first (counted as free in the check).
+    void pool_cover_step(int n, hipStream_t st) {
+        if (!pooled() || !row_pos) return;
+        mirror_rows(st);
+        const int gen_step = ints_h[1];
+        int need = 0, avail = (int)pool_free.size();
+        std::vector<int> want(B, 0);
+        for (int b = 0; b < B; ++b) {
+            if (!row_unf_h[b]) { avail += pool_held(b); continue; }
+            const int left = std::max(0, sg.tab[b].max_new_tokens - 1 - (gen_step - sg.tab[b].origin));
+            want[b] = cdiv(row_len_h[b] + std::min(n, left), 16);
+            need += std::max(0, want[b] - pool_held(b));
+        }
+        if (need > avail)
+            throw Error(QTTS_ERR_LIMIT, "stream_step: the KV page pool cannot cover the step (" + std::to_string(need) + " pages needed, " +
+                                            std::to_string(avail) + " free of " + std::to_string(pool_pages) + "); evict a row (qtts_talker_stream_evict) or step fewer frames");
+        for (int b = 0; b < B; ++b)
+            if (!row_unf_h[b]) pool_release(b);
+        for (int b = 0; b < B; ++b)
+            if (row_unf_h[b]) pool_grant(b, want[b]);
+        pool_flush(st);
+    }
     bool any_graph() const { return graph_exec != nullptr || !graph_long.empty(); }
     // the captured graph for the mode a burst ending at `kv_len_after` keys runs in, capturing `step` (which is NOT executed by
     // the capture) on first use
@@ -877,13 +961,16 @@ void qtts_talker::finalize() {
     if (has_proj && G > 2) weight_bytes_frame -= (G - 2) * eb * (double)cd.H * td.H;   // only pass 0 still runs the projection
     if (G > 2) weight_bytes_frame -= (G - 2) * eb * (double)(cd.qd + 2 * cd.kvd) * cd.H;   // layer-0 qkv GEMM of passes >= 1
 
-    // ---- KV caches (pages of 16 tokens, reserved up front)
+    // ---- KV caches (pages of 16 tokens, reserved up front; the talker's: or a shared pool of pool_pages + the sink)
     const size_t esz = bf16 ? 2 : 4;
     const int pps = cdiv(c.max_seq, 16);
     // bf16 talker cache: V pages transposed ([dim][16 keys]) -- the A-operand image of the PV product of attn_tk16_kernel, which runs
     // both attention products on the matrix pipe (QTTS_ATTN_MFMA=0: the VALU kernel attn_tk on row-major V pages, for A/B runs)
     const bool attn_mfma = bf16 && QTTS_OPT_ON("QTTS_ATTN_MFMA");
     kv_t = {nullptr, nullptr, nullptr, pps, pps * c.max_batch, td.nkv, td.hd, bf16 ? 1 : 0, 1, attn_mfma ? 1 : 0};
+    if (pooled()) {                   // a shared pool (qtts_talker_set_kv_pool): pool_pages granted on demand + the sink, read through the table
+        kv_t.n_pages = pool_pages + 1; kv_t.contig = 0;
+    }
     const size_t tb = (size_t)c.num_hidden_layers * kv_t.n_pages * td.nkv * 16 * td.hd * esz;
     kpool_t.alloc(tb); vpool_t.alloc(tb);
     QTTS_CHECK_HIP(hipMemset(kpool_t.p, 0, tb)); QTTS_CHECK_HIP(hipMemset(vpool_t.p, 0, tb));
@@ -894,7 +981,13 @@ void qtts_talker::finalize() {
     QTTS_CHECK_HIP(hipMemset(kpool_c.p, 0, cb)); QTTS_CHECK_HIP(hipMemset(vpool_c.p, 0, cb));
     {
         std::vector<int> t((size_t)c.max_batch * pps), u((size_t)c.max_batch * cpps);
-        for (size_t i = 0; i < t.size(); ++i) t[i] = (int)i;
+        for (size_t i = 0; i < t.size(); ++i) t[i] = pooled() ? pool_pages : (int)i;      // (a pool: every entry names the sink until a grant)
+        if (pooled()) {
+            ptab_h = t;
+            pool_row.assign(c.max_batch, {});
+            pool_free.resize(pool_pages);
+            for (int i = 0; i < pool_pages; ++i) pool_free[i] = pool_pages - 1 - i;      // (the first grants are pages 0, 1, 2, ...)
+        }
         for (size_t i = 0; i < u.size(); ++i) u[i] = (int)i;
         ptab_t.upload(t.data(), t.size() * 4); ptab_c.upload(u.data(), u.size() * 4);
     }
@@ -1039,8 +1132,16 @@ void qtts_talker::prefill(const float* embeds, int B_, int T, const int32_t* n_p
     QTTS_REQUIRE(B_ >= 1 && B_ <= c.max_batch, QTTS_ERR_LIMIT, "talker: batch exceeds max_batch");
     QTTS_REQUIRE(T >= 1 && T < c.max_seq, QTTS_ERR_LIMIT, "talker: prompt longer than max_seq");
     QTTS_REQUIRE(Tt_ >= 1, QTTS_ERR_ARG, "talker: trailing_text_hidden must have >= 1 row");
+    for (int b = 0; b < B_; ++b) QTTS_REQUIRE(n_pad_host[b] >= 0 && n_pad_host[b] < T, QTTS_ERR_ARG, "talker: n_pad out of range");
+    if (pooled()) {                   // a prefill restarts every row: all pages come back, each row of the batch takes its prompt's
+        const int want = cdiv(T, 16);
+        if (B_ * want > pool_pages)
+            throw Error(QTTS_ERR_LIMIT, "talker: the prompts need " + std::to_string(B_ * want) + " KV pages, the pool has " + std::to_string(pool_pages));
+        for (int b = 0; b < c.max_batch; ++b) pool_release(b);
+        for (int b = 0; b < B_; ++b) pool_grant(b, want);
+        pool_flush(st);
+    }
     B = B_; T0 = T; Tt = Tt_;
-    for (int b = 0; b < B; ++b) QTTS_REQUIRE(n_pad_host[b] >= 0 && n_pad_host[b] < T, QTTS_ERR_ARG, "talker: n_pad out of range");
     const int M = B * T, H = td.H;
     pf_x.ensure((size_t)M * H * 4);
     trailing.ensure((size_t)B * Tt * H * 4); tts_pad.ensure((size_t)H * 4);
@@ -1420,6 +1521,13 @@ void qtts_talker::admit(int n_new, const int32_t* rows_host, const float* embeds
     }
     if (!row_pos && T > kv_len)       // (every prompt fits, the group's padded length does not)
         fail(QTTS_ERR_LIMIT, rows_host[0], "the group's padded length T (" + std::to_string(T) + ") is longer than the stream's position (" + std::to_string(kv_len) + ")");
+    if (pooled() && row_pos) {        // the group's prompt pages must fit (the rows' previous occupants give theirs back first)
+        int need = 0, avail = (int)pool_free.size();
+        for (int i = 0; i < n_new; ++i) { need += cdiv(T, 16); avail += pool_held(rows_host[i]); }
+        if (need > avail)
+            throw Error(QTTS_ERR_LIMIT, std::string(who) + ": the KV page pool cannot hold the group's prompts (" + std::to_string(need) + " pages needed, " +
+                                            std::to_string(avail) + " free of " + std::to_string(pool_pages) + ")");
+    }
     // ---- from here on the call writes
     // per-row positions: the prompt goes to slots [0, T) of the row and the row's length restarts at T -- nothing of the previous occupant
     // is read again: its keys lie at or above the new length, or are overwritten
@@ -1430,6 +1538,11 @@ void qtts_talker::admit(int n_new, const int32_t* rows_host, const float* embeds
         row_fast_t = fast_t; row_fast_c = fast_c;
         destroy_graph(); graph_nodes = 0;
         graph_key.row_fast_t = row_fast_t; graph_key.row_fast_c = row_fast_c;
+    }
+    if (pooled() && row_pos) {
+        for (int i = 0; i < n_new; ++i) pool_release(rows_host[i]);
+        for (int i = 0; i < n_new; ++i) pool_grant(rows_host[i], cdiv(T, 16));
+        pool_flush(st);
     }
     pf_x.ensure((size_t)M * H * 4);
     adm_rows_d.ensure((size_t)64 * 4); adm_npad_d.ensure((size_t)64 * 4);
@@ -1513,6 +1626,8 @@ static void generate_body(qtts_talker* t, const qtts_sampling* sp, const RowTabl
                           int32_t eos_token_id, const int32_t* suppress_host, int32_t n_suppress, int64_t* codes_dev,
                           float* hidden_dev, int64_t* tokens_dev, int32_t* n_frames_host, hipStream_t st) {
     const int B = t->B;
+    // (a pooled engine: the call's worst case is reserved before it begins, so it cannot starve mid-flight; refused, the prefill stays)
+    t->pool_reserve_rows(B, cdiv(t->T0 + max_new_tokens, 16), "generate", st);
     upload_call_state(t, *sp, rt, max_new_tokens, suppress_host, n_suppress, st);
     const int max_frames = std::max(1, max_new_tokens - 1);
     t->frames_run = 0;
@@ -1676,6 +1791,10 @@ static void stream_launch_frames(qtts_talker* t, int n, hipStream_t st) {
 static void stream_begin_body(qtts_talker* t, const qtts_sampling* sp, const RowTable* rt, int32_t max_new_tokens, int32_t min_new_tokens,
                               int32_t eos_token_id, const int32_t* suppress_host, int32_t n_suppress, int64_t* codes_dev,
                               float* hidden_dev, hipStream_t st, int max_row = 0, bool row_positions = false) {
+    // a pooled engine: a stream with per-row positions takes its pages step by step (pool_cover_step); every other stream reserves its
+    // worst case now -- prompt + limit, or whole rows where admissions follow the shared position up to max_seq
+    if (!row_positions)
+        t->pool_reserve_rows(t->B, max_row > 0 ? t->kv_t.pages_per_seq : cdiv(t->T0 + max_new_tokens, 16), "stream_begin", st);
     upload_call_state(t, *sp, rt, max_row > 0 ? max_row : max_new_tokens, suppress_host, n_suppress, st);
     if (row_positions) {          // every row starts at the prefill's position (the first sample_finish makes T0 - 1 the T0 of a running row)
         std::vector<int> len0(t->B, t->T0 - 1);
@@ -1787,6 +1906,51 @@ int qtts_talker_stream_row_lens(qtts_talker* t, int32_t* lens_host) {
     QTTS_API_END
 }
 
+int qtts_talker_set_kv_pool(qtts_talker* t, int32_t n_pages) {
+    QTTS_API_BEGIN
+    QTTS_REQUIRE(t, QTTS_ERR_ARG, "null handle");
+    QTTS_REQUIRE(!t->finalized, QTTS_ERR_STATE, "set_kv_pool after finalize");
+    QTTS_REQUIRE(n_pages >= 0, QTTS_ERR_ARG, "set_kv_pool: n_pages >= 0");
+    const int one_row = cdiv(t->cfg.max_seq, 16);
+    if (n_pages != 0 && n_pages < one_row)
+        throw Error(QTTS_ERR_LIMIT, "set_kv_pool: " + std::to_string(n_pages) + " pages do not hold one request of max_seq keys (" + std::to_string(one_row) + " pages)");
+    t->pool_pages = n_pages;
+    QTTS_API_END
+}
+
+int qtts_talker_stream_kv(qtts_talker* t, int32_t* pages_host, int32_t* free_host, int32_t* pool_host) {
+    QTTS_API_BEGIN
+    QTTS_REQUIRE(t && pages_host && free_host && pool_host, QTTS_ERR_ARG, "null argument");
+    QTTS_REQUIRE(t->finalized && t->pooled(), QTTS_ERR_STATE, "stream_kv: the engine has no KV page pool (qtts_talker_set_kv_pool before finalize)");
+    for (int b = 0; b < t->B; ++b) pages_host[b] = t->pool_held(b);
+    *free_host = (int32_t)t->pool_free.size();
+    *pool_host = t->pool_pages;
+    QTTS_API_END
+}
+
+int qtts_talker_stream_evict(qtts_talker* t, int32_t n, const int32_t* rows_host) {
+    QTTS_API_BEGIN
+    QTTS_REQUIRE(t && rows_host, QTTS_ERR_ARG, "null argument");
+    QTTS_REQUIRE(t->sg.active && t->row_pos, QTTS_ERR_STATE, "stream_evict: no stream with per-row positions is open (qtts_talker_stream_begin_admitting_rows first)");
+    const int B = t->B;
+    QTTS_REQUIRE(n >= 1 && n <= B, QTTS_ERR_ARG, "stream_evict: 1 <= n <= the stream's rows");
+    std::vector<char> seen(B, 0);
+    for (int i = 0; i < n; ++i) {
+        const int b = rows_host[i];
+        QTTS_REQUIRE(b >= 0 && b < B, QTTS_ERR_ARG, "stream_evict: row " + std::to_string(b) + " is not a row of this stream (" + std::to_string(B) + " rows)");
+        QTTS_REQUIRE(!seen[b], QTTS_ERR_ARG, "stream_evict: row " + std::to_string(b) + ": listed twice");
+        seen[b] = 1;
+    }
+    // ---- from here on the call writes: the occupants are abandoned (finished on the device, lengths frozen where they are)
+    hipStream_t st = t->sg.st;
+    const int zero = 0;
+    for (int i = 0; i < n; ++i) QTTS_CHECK_HIP(hipMemcpyAsync(t->ss.unfinished + rows_host[i], &zero, 4, hipMemcpyHostToDevice, st));
+    QTTS_CHECK_HIP(hipStreamSynchronize(st));
+    t->mirror_rows(st);
+    t->pool_release_finished(st);
+    QTTS_API_END
+}
+
 int qtts_talker_stream_admit(qtts_talker* t, int32_t n_new, const int32_t* rows_host, const float* embeds_dev, int32_t T, const int32_t* n_pad_host,
                              const float* trailing_dev, int32_t Tt, const qtts_row_sampling* settings_host, void* stream) {
     QTTS_API_BEGIN
@@ -1819,7 +1983,7 @@ int qtts_talker_stream_rows(qtts_talker* t, int32_t* unfinished_host, int32_t* f
         frames_host[b] = e < n_row ? e : std::min(std::max(0, n_row - 1), g.max_frames);
     }
     *kv_len_host = fin[2];
-    if (t->row_pos) { t->mirror_rows(g.st); *kv_len_host = t->longest_row(); }
+    if (t->row_pos) { t->mirror_rows(g.st); *kv_len_host = t->longest_row(); t->pool_release_finished(g.st); }
     QTTS_API_END
 }
 
@@ -1831,8 +1995,10 @@ int qtts_talker_stream_step(qtts_talker* t, int32_t max_frames_now, int32_t* fra
     QTTS_REQUIRE(max_frames_now >= 1, QTTS_ERR_ARG, "max_frames_now >= 1");
     hipStream_t st = (hipStream_t)stream;
     auto& g = t->sg;
+    t->pool_cover_step(max_frames_now, st);          // (refused with QTTS_ERR_LIMIT: nothing has changed)
     stream_launch_frames(t, max_frames_now, st);
     QTTS_CHECK_HIP(hipStreamSynchronize(st));
+    if (t->pooled() && t->row_pos) { t->mirror_rows(st); t->pool_release_finished(st); }
     int fin[6];
     copy_on_stream(fin, t->ss.n_generated, sizeof(fin), hipMemcpyDeviceToHost, st);
     if (fin[5]) g.active = false;                        // (no packet of a burst that lost a fused launch is handed out)
@@ -1878,6 +2044,15 @@ int qtts_talker_debug_logits(qtts_talker* t, float* logits_dev, void* stream) {
     QTTS_REQUIRE(t && logits_dev, QTTS_ERR_ARG, "null argument");
     QTTS_CHECK_HIP(hipMemcpyAsync(logits_dev, t->logits.p, (size_t)t->B * t->cfg.vocab_size * 4, hipMemcpyDeviceToDevice,
                                   (hipStream_t)stream));
+    QTTS_API_END
+}
+int qtts_talker_debug_kv_table(qtts_talker* t, int32_t row, int32_t* entries_host, void* stream) {
+    QTTS_API_BEGIN
+    QTTS_REQUIRE(t && entries_host, QTTS_ERR_ARG, "null argument");
+    QTTS_REQUIRE(t->finalized, QTTS_ERR_STATE, "debug_kv_table before finalize");
+    QTTS_REQUIRE(row >= 0 && row < t->cfg.max_batch, QTTS_ERR_ARG, "debug_kv_table: row " + std::to_string(row) + " is not a row of this engine");
+    const int pps = t->kv_t.pages_per_seq;         // (the DEVICE table: what the kernels of the next launch on `stream` read)
+    copy_on_stream(entries_host, t->ptab_t.as<int>() + (size_t)row * pps, (size_t)pps * 4, hipMemcpyDeviceToHost, (hipStream_t)stream);
     QTTS_API_END
 }
 int qtts_talker_debug_cp_logits(qtts_talker* t, float* logits_dev, void* stream) {

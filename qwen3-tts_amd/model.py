@@ -179,14 +179,16 @@ class Qwen3TTSForConditionalGeneration:
 
     def __init__(self, config: Any, state_dict: Dict[str, torch.Tensor], device: str = "cuda:0",
                  dtype: torch.dtype = torch.bfloat16, max_batch: int = 8, max_seq: int = 4096,
-                 use_graph: bool = True):
+                 use_graph: bool = True, kv_pages: Optional[int] = None):
+        """`kv_pages`: the talker's KV cache as a shared pool of that many 16-key pages (`TalkerEngine(kv_pages=...)`); None: the static
+        max_batch x max_seq layout."""
         self.config = TalkerConfig.from_any(config)
         self.dtype = dtype
         sd = state_dict
         if any(k.startswith("talker.") for k in sd):
             sd = {k[len("talker."):]: v for k, v in sd.items() if k.startswith("talker.")}
         self.talker = TalkerEngine(self.config, sd, weight_dtype=dtype, device=device, max_batch=max_batch,
-                                   max_seq=max_seq, use_graph=use_graph)
+                                   max_seq=max_seq, use_graph=use_graph, kv_pages=kv_pages)
         self.device = self.talker.device            # (the HIP device the engine accepted: `_lib.hip_device` refuses anything else)
         if "model.text_embedding.weight" not in sd:
             raise KeyError("state_dict has no talker.model.text_embedding.weight (needed by the prompt assembly)")
@@ -443,7 +445,8 @@ class Qwen3TTSModel:
     @classmethod
     def from_pretrained(cls, pretrained_model_name_or_path: str, **kwargs) -> "Qwen3TTSModel":
         """Same kwargs as the reference (qwen3_tts_model.py:82-121): `device_map`, `dtype`,
-        `attn_implementation` (accepted; the HIP engine has one attention path)."""
+        `attn_implementation` (accepted; the HIP engine has one attention path).  `kv_pages`: the talker's KV cache as a shared page
+        pool of that size (`TalkerEngine(kv_pages=...)`; `TalkerEngine.kv_page_bytes` per page); None: max_batch x max_seq keys."""
         from safetensors.torch import load_file
         from .codec import Qwen3TTSTokenizer
         path = resolve_checkpoint_dir(pretrained_model_name_or_path, **kwargs)
@@ -467,7 +470,8 @@ class Qwen3TTSModel:
             want = int((gen_cfg or {}).get("max_new_tokens", 2048) or 2048)
             max_seq = min(16384, ((want + 1024 + 255) // 256) * 256)
         model = Qwen3TTSForConditionalGeneration(cfg, sd, device=device, dtype=dtype,
-                                                 max_batch=kwargs.get("max_batch", 8), max_seq=int(max_seq))
+                                                 max_batch=kwargs.get("max_batch", 8), max_seq=int(max_seq),
+                                                 kv_pages=kwargs.get("kv_pages"))
         st_dir = os.path.join(path, "speech_tokenizer")                       # M:1900-1920
         if os.path.isdir(st_dir):
             model.load_speech_tokenizer(Qwen3TTSTokenizer.from_pretrained(st_dir, device_map=device, dtype=dtype,
@@ -719,7 +723,14 @@ class Qwen3TTSModel:
         decoder (`CodecDecoderEngine.stream_push_rows`), which decodes only the new frames of a packet; `left_context_size` is NOT
         used under this schedule, and a request's concatenated audio equals the whole-sequence `forward` of its codes, not the
         chunked rule.  The codec must have been built with a `max_batch` of at least the talker's.  `schedule="continuous"`: the same
-        on the talker's stream with per-row positions (the codec slots are keyed by row either way)."""
+        on the talker's stream with per-row positions (the codec slots are keyed by row either way).
+
+        On a model with a KV page pool (`kv_pages`) the continuous schedule may preempt a request and start it again at frame 0
+        (`RefillRow.restart`).  The request's codec slot is reset as for any request that starts, the replayed frames are pushed
+        through it to rebuild the decoder's state, and only the PCM beyond what the request has already delivered is yielded (frames
+        are a fixed number of samples, so that is a sample count): no sample is delivered twice.  This rests on the replayed codes
+        being the delivered ones -- a request's codes depend on its seed and its own step, not on its schedule -- which the tests pin
+        in fp32; in bf16 the same holds run to run on one engine (the arithmetic of a row does not depend on its neighbours)."""
         if self.model.tts_model_type != "custom_voice":
             raise self._unsupported("stream_custom_voice")
         texts = self._ensure_list(text)
@@ -749,12 +760,16 @@ class Qwen3TTSModel:
                                  f"the talker's ({rows}); every talker row needs a slot of the codec stream")
             sr = int(self.model.speech_tokenizer.model.output_sample_rate)
             dec.stream_begin(rows)
+            made, delivered = [0] * len(texts), [0] * len(texts)      # samples decoded since the request (re)started / handed out
             for record in self.model.generate_stream(input_ids=input_ids, instruct_ids=self._instruct_ids(instructs), languages=languages,
                                                      speakers=speakers, non_streaming_mode=non_streaming_mode,
                                                      packet_frames=packet_frames, **gen_kwargs):
                 started = [e.row for e in record.rows if e.first]
                 if started:
                     dec.stream_reset_rows(started)
+                for e in record.rows:
+                    if e.first:
+                        made[e.request] = 0
                 live = [e for e in record.rows if e.codes.shape[0] > 0]
                 if not live:
                     continue
@@ -770,7 +785,12 @@ class Qwen3TTSModel:
                 up = wav.shape[-1] // k
                 out = [np.zeros(0, np.float32) for _ in texts]
                 for m, e in enumerate(live):
-                    out[e.request] = wav[m, : int(e.codes.shape[0]) * up].cpu().numpy().astype(np.float32)
+                    seg = wav[m, : int(e.codes.shape[0]) * up]
+                    r, at = e.request, made[e.request]
+                    made[r] = at + int(seg.shape[0])
+                    if made[r] > delivered[r]:           # (a replay after a restart: only what lies beyond the delivered samples)
+                        out[r] = seg[max(0, delivered[r] - at):].cpu().numpy().astype(np.float32)
+                        delivered[r] = made[r]
                 yield out, sr
             return
         stream = dec.stream(left_context_size)

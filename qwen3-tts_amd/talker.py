@@ -47,6 +47,8 @@ class RefillRow:
     first: bool                # the request started with this packet: whatever the row held before belongs to another request
     last: bool                 # the request finished: its frames end here (first eos in codebook 0, or its own limit)
     hidden: Optional[torch.Tensor] = None        # (k, H) float32 `past_hidden` of these frames, when asked for
+    restart: bool = False      # (pooled engines) the request was preempted and starts again at frame 0 with this packet: set together with
+                               # `first`; drop what was collected for it -- the replayed frames equal the dropped ones
 
 
 @dataclass
@@ -120,8 +122,14 @@ class TalkerEngine:
     """Owns one `qtts_talker` handle."""
 
     def __init__(self, config: Any, state_dict: Dict[str, torch.Tensor], weight_dtype: torch.dtype = torch.bfloat16,
-                 device: str = "cuda:0", max_batch: int = 8, max_seq: int = 4096, use_graph: bool = True, shared_device: bool = False):
-        """`shared_device`: this engine will run BESIDE another talker engine on the same device (a throughput job with several engines per GPU:
+                 device: str = "cuda:0", max_batch: int = 8, max_seq: int = 4096, use_graph: bool = True, shared_device: bool = False,
+                 kv_pages: Optional[int] = None):
+        """`kv_pages`: the talker's KV cache as a shared pool of that many 16-key pages (`kv_page_bytes` each) instead of `max_batch` x
+        `max_seq` keys reserved per row (include/qtts.h `qtts_talker_set_kv_pool`); at least ceil(max_seq / 16).  A continuous stream then
+        takes pages as its rows grow and `generate(schedule="continuous")` preempts by restart when the pool runs dry (`_refill_stream`);
+        every other call reserves its worst case when it begins.  None: the static layout.
+
+        `shared_device`: this engine will run BESIDE another talker engine on the same device (a throughput job with several engines per GPU:
         bench.py --workload clone-shard, `sharding.engine_partition`).  It then keeps the decode GEMMs where an engine that has the device to
         itself runs the code predictor's MLP as one launch at batch 9..32 (csrc/cp_mlp32.hip): that launch's workgroups wait for each other, and
         behind another engine's kernels they are placed one by one and spin meanwhile -- measured on the MI355X, two engines x waves of 32:
@@ -130,6 +138,7 @@ class TalkerEngine:
         self.device = _lib.hip_device(device, "TalkerEngine")
         self.weight_dtype = weight_dtype
         self.max_batch, self.max_seq = int(max_batch), int(max_seq)
+        self.kv_pages = int(kv_pages) if kv_pages else None
         self._lib = _lib.load_library()
         self._lock = threading.RLock()
         c = self.config
@@ -147,6 +156,8 @@ class TalkerEngine:
         import contextlib
         with torch.cuda.device(self.device), (_lib.options(QTTS_CP_MLP32="0") if shared_device else contextlib.nullcontext()):
             _lib.check(self._lib.qtts_talker_create(C.byref(tc), C.byref(self._h)))
+            if self.kv_pages:
+                _lib.check(self._lib.qtts_talker_set_kv_pool(self._h, self.kv_pages))
             has_prefix = any(k.startswith("talker.") for k in state_dict)
             for name, t in state_dict.items():
                 if has_prefix:
@@ -171,6 +182,13 @@ class TalkerEngine:
 
     def _s(self):
         return C.c_void_p(self._stream.cuda_stream)
+
+    @property
+    def kv_page_bytes(self) -> int:
+        """Bytes of one 16-key page of the talker cache over all layers, K and V: layers x 2 x kv heads x 16 x head_dim x element size
+        (1.7B dims in bf16: 28 x 2 x 8 x 16 x 128 x 2 B = 1.835 MB)."""
+        c = self.config
+        return int(c.num_hidden_layers) * 2 * int(c.num_key_value_heads) * 16 * int(c.head_dim) * (2 if self.weight_dtype == torch.bfloat16 else 4)
 
     @_lib.locked
     def set_profile(self, enable):
@@ -633,6 +651,31 @@ class TalkerEngine:
         return list(lens)
 
     @_lib.locked
+    def stream_kv(self):
+        """`qtts_talker_stream_kv` on a pooled engine: (pages held by each row of the last prefill's batch, free pages, pool size)."""
+        B = getattr(self, "_live_batch", self.max_batch)
+        pages, free, pool = (C.c_int32 * B)(), C.c_int32(0), C.c_int32(0)
+        _lib.check(self._lib.qtts_talker_stream_kv(self._h, pages, C.byref(free), C.byref(pool)))
+        return list(pages), int(free.value), int(pool.value)
+
+    @_lib.locked
+    def debug_kv_table(self, row: int) -> List[int]:
+        """`qtts_talker_debug_kv_table`: the device page table of one row of the talker cache, ceil(max_seq / 16) entries in slot order
+        (pooled: an entry without a grant holds `kv_pages`, the sink)."""
+        ent = (C.c_int32 * (-(-self.max_seq // 16)))()
+        with torch.cuda.device(self.device), torch.cuda.stream(self._stream):
+            _lib.check(self._lib.qtts_talker_debug_kv_table(self._h, int(row), ent, self._s()))
+        return list(ent)
+
+    @_lib.locked
+    def stream_evict(self, row_ids: List[int]):
+        """`qtts_talker_stream_evict`: abandon the occupants of the listed rows of the open stream with per-row positions (preemption by
+        restart, or cancelling a request); their pages go back to the pool."""
+        ids_c = (C.c_int32 * max(1, len(row_ids)))(*[int(x) for x in row_ids])
+        with torch.cuda.device(self.device), torch.cuda.stream(self._stream):
+            _lib.check(self._lib.qtts_talker_stream_evict(self._h, len(row_ids), ids_c))
+
+    @_lib.locked
     def stream_step(self, max_frames_now: int):
         """`qtts_talker_stream_step` on the open stream: (frame steps the stream has run, whether its stop condition has latched)."""
         total, fin = C.c_int32(0), C.c_int32(0)
@@ -672,7 +715,24 @@ class TalkerEngine:
         after every packet every queued request for which a row is free is admitted, in queue order (a group whose padded length would
         push one of its members past max_seq is split into several `stream_admit` calls) -- and ONE stream serves the whole call, at
         full width: the opening group is the widest that fits (`_widest_opener`) and the remaining rows start as spare rows.
-        `last_refill["max_row_len"]` is the largest row length seen."""
+        `last_refill["max_row_len"]` is the largest row length seen.
+
+        On an engine with a KV page pool (`kv_pages`) the continuous schedule is optimistic: rows take pages as they grow and nobody
+        reserves a worst case.  Admission: after each packet, in queue order, only while the group's prompt pages fit AND one page per row
+        that would then be running stays free (the watermark keeps a preempted request from being admitted straight into the next
+        preemption; a pool that holds max_seq keys for every row can never run dry and admits like the static engine).  Before each `stream_step(packet_frames)`: while the pool cannot cover the step, the running request with the
+        fewest frames (ties: the highest request index) is evicted (`stream_evict`) and returns to the FRONT of the queue; the only
+        running row is never evicted, and the request with the most frames always keeps running, finishes and frees its pages, so the
+        call terminates.  A re-admitted request starts again at frame 0: its first packet carries `first=True, restart=True`.  Its codes
+        are the same as before (a request's draws depend on its seed and its own step only).  `last_refill` reports `pool_pages`,
+        `peak_pages` and `preemptions`.  The other schedules on a pooled engine reserve their worst case when a stream begins.
+
+        Width on a pooled engine: the opening group's prompts (the spare rows' copies of the first prompt included) must fit the pool,
+        so the stream opens with at most `kv_pages // ceil(longest opening prompt / 16)` rows -- and a stream keeps its opening width
+        for the whole call.  A pool that is tight against a long first prompt therefore serves the whole request list on that narrower
+        stream, also after the long prompt has retired and its pages are free (`last_refill["occupancy"]` is measured against
+        `max_batch` and shows it).  It costs throughput, never correctness; size the pool to at least
+        `max_batch x ceil(longest prompt / 16)` pages to open at full width."""
         c, dev = self.config, self.device
         if inputs_embeds.dim() != 3 or inputs_embeds.shape[-1] != c.hidden_size:
             raise ValueError(f"inputs_embeds must be (B, T, {c.hidden_size})")
@@ -705,8 +765,43 @@ class TalkerEngine:
         mb = self.max_batch
         max_row = max(int(rows[i].max_new_tokens) for i in range(N))
         queue = sorted(range(N), key=lambda i: (-lens[i], i))
-        st = dict(streams=0, admit_calls=0, admitted_rows=0, frames_run=0, row_frames=0, graph_captures=0, max_row_len=0)
+        st = dict(streams=0, admit_calls=0, admitted_rows=0, frames_run=0, row_frames=0, graph_captures=0, max_row_len=0,
+                  pool_pages=self.kv_pages or 0, peak_pages=0, preemptions=0)
         limit = lambda i: int(rows[i].max_new_tokens)
+        pooled = bool(row_positions and self.kv_pages)
+        # (a pool that holds max_seq keys for every row can never run dry: nothing is preempted, so admission is not held back either)
+        tight = pooled and self.kv_pages < self.max_batch * (-(-self.max_seq // 16))
+        pages_of = lambda n_keys: -(-int(n_keys) // 16)
+        restarted = set()
+
+        def step_need(slot, seen):
+            """the host's page count of the next packet: (pages the running rows still need, pages free once the finished rows have given
+            theirs back, pages in use during the packet) -- the engine's own rule (include/qtts.h, stream_step on a pooled engine)"""
+            held, free, _ = self.stream_kv()
+            row_len = self.stream_row_lens()
+            need, avail, used = 0, free, 0
+            for b, r in enumerate(slot):
+                if r is None:
+                    avail += held[b]
+                    continue
+                want = pages_of(row_len[b] + min(packet_frames, max(0, limit(r) - 1 - seen[b])))
+                need += max(0, want - held[b])
+                used += max(want, held[b])
+            return need, avail, used
+
+        def admissible(free_rows, running):
+            """pooled: the head of the queue that fits -- prompt pages of its admission groups + one page per row then running <= free"""
+            if not tight:
+                return queue[:len(free_rows)]
+            _, free, _ = self.stream_kv()
+            take = []
+            for i in queue[:len(free_rows)]:
+                cand = take + [i]
+                prompt_pages = sum(len(grp) * pages_of(max(lens[j] for j in grp)) for grp in admission_groups(cand))
+                if prompt_pages + (running + len(cand) if running or take else 0) > free:
+                    break
+                take = cand
+            return take
 
         def admission_groups(idx):
             """per-row positions: `idx` in queue order, cut into groups in each of which the padded length + every limit fits max_seq"""
@@ -739,6 +834,10 @@ class TalkerEngine:
                         # limit 1, finished with their token 0 -- that the first admission fills
                         first = self._widest_opener(queue, lens, [limit(i) for i in range(N)], self.max_seq, mb)
                         spare = min(mb, N) - len(first)
+                        if pooled:        # the opening prompts (the spare rows' copies included) must fit the pool
+                            width = max(1, self.kv_pages // pages_of(max(lens[i] for i in first)))
+                            first = first[:width]
+                            spare = min(spare, width - len(first))
                     queue = [i for i in queue if i not in first]
                     e, npd, tr, tab = group(first + first[:1] * spare)
                     for k in range(len(first), len(first) + spare):
@@ -748,6 +847,20 @@ class TalkerEngine:
                     slot, seen, fresh = list(first) + [None] * spare, [0] * (len(first) + spare), set(first)
                     try:
                         while any(r is not None for r in slot):
+                            if pooled:
+                                while True:
+                                    need, avail, used = step_need(slot, seen)
+                                    running = [b for b, r in enumerate(slot) if r is not None]
+                                    if need <= avail or len(running) <= 1:
+                                        break
+                                    victim = min(running, key=lambda b: (seen[b], -slot[b]))
+                                    self.stream_evict([victim])
+                                    queue.insert(0, slot[victim])
+                                    restarted.add(slot[victim])
+                                    fresh.discard(slot[victim])
+                                    slot[victim] = None
+                                    st["preemptions"] += 1
+                                st["peak_pages"] = max(st["peak_pages"], used)
                             self.stream_step(packet_frames)
                             unfinished, frames, kv_len = self.stream_rows()
                             packet = []
@@ -757,8 +870,10 @@ class TalkerEngine:
                                 done, k0, k1 = not unfinished[b], seen[b], frames[b]
                                 if k1 > k0 or done:
                                     packet.append(RefillRow(request=r, row=b, codes=codes[b, k0:k1].clone(), first=r in fresh, last=done,
-                                                            hidden=hidden[b, k0:k1].clone() if hidden is not None else None))
+                                                            hidden=hidden[b, k0:k1].clone() if hidden is not None else None,
+                                                            restart=r in fresh and r in restarted))
                                     fresh.discard(r)
+                                    restarted.discard(r)
                                     seen[b] = k1
                                 if done:
                                     st["row_frames"] += k1
@@ -766,7 +881,7 @@ class TalkerEngine:
                             yield RefillPacket(packet)
                             free = [b for b, r in enumerate(slot) if r is None]
                             if row_positions:
-                                take = queue[:len(free)]
+                                take = admissible(free, len(slot) - len(free)) if pooled else queue[:len(free)]
                                 at = 0
                                 for grp in admission_groups(take):
                                     e, npd, tr, tab = group(grp)
@@ -827,6 +942,8 @@ class TalkerEngine:
                                           output_hidden_states=output_hidden_states, seed=seed, packet_frames=packet_frames,
                                           row_positions=row_positions):
             for e in packet.rows:
+                if e.restart:         # a preempted request starts again at frame 0: what it had delivered is replayed
+                    parts[e.request], hparts[e.request] = [], []
                 parts[e.request].append(e.codes)
                 hparts[e.request].append(e.hidden)
         out_codes = [torch.cat(p) for p in parts]

@@ -133,6 +133,22 @@ def waits_inside_burst(ins, n_loads):
     return [i for i in range(lo, hi) if re.match(r"s_waitcnt vmcnt\(\d+\)", ins[i])]
 
 
+def first_burst(ins):
+    """Number of global loads a kernel issues before its first `s_waitcnt vmcnt(..)` behind its first load: the length of the request
+    burst it opens with (scalar loads count on lgkmcnt and are not part of it)."""
+    loads = [i for i, l in enumerate(ins) if is_load(l)]
+    if not loads: return 0
+    wait = next((i for i in range(loads[0], len(ins)) if re.match(r"s_waitcnt vmcnt\(\d+\)", ins[i])), len(ins))
+    return sum(1 for i in loads if i < wait)
+
+
+def scalar_loads_before(ins, n_loads):
+    """Scalar loads (`s_load_*`) issued before the n_loads-th global load of a kernel."""
+    loads = [i for i, l in enumerate(ins) if is_load(l)]
+    if len(loads) < n_loads: return None
+    return sum(1 for l in ins[:loads[n_loads - 1]] if l.startswith("s_load_"))
+
+
 def scan(lib, window=40, max_n=1, name_filter=""):
     rows = []
     for name, ins in kernels(lib).items():
