@@ -55,7 +55,8 @@ const char* qtts_last_error(void);
  * added, no signature and no struct layout changed; a binding that needs them finds out by looking the symbols up; still 15:
  * + qtts_talker_stream_begin_admitting_rows, qtts_talker_stream_row_lens, qtts_talker_stream_mode -- three entry points added, no
  * signature and no struct layout changed: qtts_talker_stats is byte for byte what it was, so a v15 binding keeps working and one that
- * needs the new calls finds out by looking the symbols up). */
+ * needs the new calls finds out by looking the symbols up; still 15: + qtts_row_warpers, qtts_talker_set_row_warpers,
+ * qtts_talker_sampler_class -- a new struct and two entry points, no existing signature or struct changed). */
 #define QTTS_ABI_VERSION 15
 int qtts_abi_version(void);
 
@@ -544,6 +545,40 @@ int qtts_talker_stream_mode(qtts_talker* t, int32_t* row_positions_host, int32_t
 int qtts_talker_set_kv_pool(qtts_talker* t, int32_t n_pages);
 int qtts_talker_stream_kv(qtts_talker* t, int32_t* pages_host /* (B) */, int32_t* free_host, int32_t* pool_host);
 int qtts_talker_stream_evict(qtts_talker* t, int32_t n, const int32_t* rows_host);
+
+/* The remaining HF sampling controls of the talker's codebook-0 sampler, per request (entry points added under ABI 15; no struct
+ * changed): the four probability warpers HF generate applies after top-p -- min_p, typical_p, epsilon_cutoff, eta_cutoff -- and
+ * no_repeat_ngram_size (transformers 4.57.3 generation/logits_process.py; the reference forwards them to generate(),
+ * qwen_tts/inference/qwen3_tts_model.py:287-352).  The chain of a row's token is
+ *   RepetitionPenalty -> NoRepeatNGram -> MinNewTokensLength -> SuppressTokens ->
+ *   [Temperature -> TopK -> TopP -> MinP -> Typical -> EpsilonCutoff -> EtaCutoff] -> argmax | softmax + draw;
+ * a greedy row skips the bracket (as HF does) and keeps the n-gram ban.  The n-gram history is the row's own generated codebook-0
+ * tokens (the prompt is embeds-only), counted from the row's origin like the repetition penalty's.  The code predictor's samplers take
+ * none of these (modeling_qwen3_tts.py:1652-1677 hands them the four subtalker_* knobs only).
+ *   set_row_warpers  one entry per row, 0 = off for every field.  ONE-SHOT: the table is consumed by the NEXT of generate_rows,
+ *                 stream_begin_rows, stream_begin_admitting, stream_begin_admitting_rows or stream_admit, whose n_rows / n_new must equal
+ *                 n_rows here -- otherwise that call fails with QTTS_ERR_ARG, nothing is changed and the table is dropped; so does a
+ *                 scalar qtts_talker_generate / qtts_talker_stream_begin with a table pending.  NULL / 0 clears a pending table.  Values
+ *                 are checked here, the message naming the row: min_p in [0, 1], typical_p in [0, 1] (1 is stored as off),
+ *                 epsilon_cutoff / eta_cutoff in [0, 1), no_repeat_ngram_size >= 0; anything else is QTTS_ERR_ARG.  A consuming call
+ *                 whose table has every field off is exactly the call without a table.  The entries live in a second device table
+ *                 beside the rows' settings: their VALUES are not part of the captured frame graph.  Whether any row of the table has
+ *                 any of them on IS (the talker's sampler is then another kernel): like the fast class it is monotone within a stream, so
+ *                 the first such occupant admitted into a stream that ran without any re-captures the visited graphs once, later ones
+ *                 do not.  A row admitted without a table gets an all-off entry.  Teacher forcing refuses the table call as before.
+ *   sampler_class the sampler kernels of the open stream or the last call, talker / code predictor: 0 launch constants (a scalar
+ *                 call), 1 sample_kernel_v2, 2 sample_kernel, 3 sample_warp_kernel (talker only).  A call of its own because
+ *                 qtts_talker_stats keeps its layout under ABI 15. */
+typedef struct qtts_row_warpers {      /* 32 bytes; 0 = off for every field */
+    float min_p;
+    float typical_p;
+    float epsilon_cutoff;
+    float eta_cutoff;
+    int32_t no_repeat_ngram_size;
+    int32_t reserved[3];
+} qtts_row_warpers;
+int qtts_talker_set_row_warpers(qtts_talker* t, const qtts_row_warpers* rows_host, int32_t n_rows);
+int qtts_talker_sampler_class(qtts_talker* t, int32_t* talker_host, int32_t* subtalker_host);
 
 /* Test/diagnostic hooks (device -> caller device buffers, after prefill / a generate call). */
 int qtts_talker_debug_logits(qtts_talker* t, float* logits_dev /* (B, vocab) */, void* stream);

@@ -55,6 +55,12 @@ class RowSamplingC(C.Structure):
                 ("reserved", C.c_int32), ("seed", C.c_uint64)]
 
 
+class RowWarpersC(C.Structure):
+    """include/qtts.h qtts_row_warpers: one request's remaining HF warpers and its n-gram ban (qtts_talker_set_row_warpers); 0 = off."""
+    _fields_ = [("min_p", C.c_float), ("typical_p", C.c_float), ("epsilon_cutoff", C.c_float), ("eta_cutoff", C.c_float),
+                ("no_repeat_ngram_size", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
 class EncoderConfigC(C.Structure):
     _fields_ = [("hidden_size", C.c_int32), ("num_filters", C.c_int32), ("num_residual_layers", C.c_int32),
                 ("n_ratios", C.c_int32), ("ratios", C.c_int32 * 8), ("kernel_size", C.c_int32), ("last_kernel_size", C.c_int32),
@@ -111,6 +117,7 @@ SYMBOLS = ["qtts_last_error", "qtts_abi_version", "qtts_set_option", "qtts_get_o
            "qtts_talker_stream_begin_admitting", "qtts_talker_stream_admit", "qtts_talker_stream_rows",
            "qtts_talker_stream_begin_admitting_rows", "qtts_talker_stream_row_lens", "qtts_talker_stream_mode",
            "qtts_talker_set_kv_pool", "qtts_talker_stream_kv", "qtts_talker_stream_evict",
+           "qtts_talker_set_row_warpers", "qtts_talker_sampler_class",
            "qtts_talker_debug_logits", "qtts_talker_debug_kv_table", "qtts_talker_debug_cp_logits", "qtts_talker_get_stats", "qtts_talker_get_gemm_profile", "qtts_talker_set_teacher",
            "qtts_talker_set_profile"]
 
@@ -210,6 +217,8 @@ def load_library():
     lib.qtts_talker_stream_kv.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     lib.qtts_talker_stream_evict.argtypes = [vp, i32, C.POINTER(C.c_int32)]
     lib.qtts_talker_debug_kv_table.argtypes = [vp, i32, C.POINTER(C.c_int32), vp]
+    lib.qtts_talker_set_row_warpers.argtypes = [vp, C.POINTER(RowWarpersC), i32]
+    lib.qtts_talker_sampler_class.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     lib.qtts_talker_stream_admit.argtypes = [vp, i32, C.POINTER(C.c_int32), f32p, i32, C.POINTER(C.c_int32), f32p, i32,
                                              C.POINTER(RowSamplingC), vp]
     lib.qtts_talker_stream_rows.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]

@@ -410,4 +410,20 @@ struct SampleParams {
 };
 void launch_sample(const SampleParams& p, hipStream_t st);
 
+// One request's remaining HF warpers and its n-gram ban (qtts_row_warpers, include/qtts.h) as sample_warp_kernel reads them: 32 bytes,
+// entry b beside rows[b]; 0 = off for every field.
+struct RowWarpers {
+    float min_p, typical_p, epsilon_cutoff, eta_cutoff;
+    int no_repeat_ngram_size;
+    int pad0, pad1, pad2;
+};
+static_assert(sizeof(RowWarpers) == 32, "sampling.hip: sample_warp_kernel reads an entry as two 16-byte blocks");
+// The talker's launch of a table whose rows use any of them: the row's whole chain -- greedy rows, any top_k, top_p -- in one kernel.
+// `s`: table mode, talker half (rows set, rows_sub == 0).
+struct SampleWarpParams {
+    SampleParams s;
+    const RowWarpers* warp;                  // [B] device
+};
+void launch_sample_warp(const SampleWarpParams& p, hipStream_t st);
+
 }  // namespace qtts

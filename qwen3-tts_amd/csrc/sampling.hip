@@ -738,6 +738,359 @@ void launch_sample(const SampleParams& p, hipStream_t st) {
     QTTS_CHECK_HIP(hipGetLastError());
 }
 
+// ---------------------------------------------------------------------------------- the remaining HF warpers + the n-gram ban
+// The talker's sampler of a table in which any row uses min_p, typical_p, epsilon_cutoff, eta_cutoff or no_repeat_ngram_size
+// (qtts_row_warpers).  One row's whole chain, transformers 4.57.3 `_get_logits_processor` order:
+//   RepetitionPenalty -> NoRepeatNGram -> MinNewTokensLength -> SuppressTokens ->
+//   [Temperature -> TopK -> TopP -> MinP -> Typical -> EpsilonCutoff -> EtaCutoff] -> argmax | softmax + draw
+// for any combination of knobs (greedy rows skip the bracket, as HF does, and keep the ban).  Entry discipline of sample_kernel_v2:
+// every independent load before the early exit, the thread's own V / 256 logits in registers (v = it * 256 + tid).  No sort: every
+// cut is a threshold.  TopK / TopP / Typical find theirs by a bit-by-bit selection over float_key -- 32 block reductions of a count or
+// of probability mass, one barrier each (partials double-buffered by round parity); MinP / Epsilon / Eta compare softmax numerators
+// with a bound.  Every reduction runs per thread over `it` ascending, then over the wave (DPP rows in a fixed order), then over the
+// four waves in a fixed order: the result depends on V alone, not on the row index, the batch or the neighbours' knobs.  A cut never
+// removes the maximum except Typical, after which the maximum is taken again.  The inverse-CDF scan runs in sample_kernel's order
+// for the row's own top_k (slot order (wave, slice, lane) for 0 < top_k <= 256, else index order), so a row without any of the new
+// knobs draws sample_kernel's token for the same u (up to rounding in the scan).  No finite score left: token 0.
+template <int EPT>
+__global__ __launch_bounds__(256) void sample_warp_kernel(SampleWarpParams pw) {
+    __shared__ float sc[EPT * 256];
+    __shared__ unsigned char ban[EPT * 256];
+    __shared__ float fred[8];
+    __shared__ int ired[8];
+    __shared__ __attribute__((aligned(16))) float scan[256];
+    __shared__ int pick_lo, pick_hi;
+    __shared__ int wpick[4], wlast[4];
+
+    QTTS_TS_BEGIN();
+    const SampleParams& p = pw.s;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int V = p.V;
+    const float* lg = p.logits + (size_t)b * p.ld;
+    // ---- 0. independent loads, all in flight together (the row's 64-byte entry and its 32-byte warper entry among them)
+    const int done = p.done_in ? *p.done_in : 0;
+    const int n_gen_s = p.n_generated_dev ? *p.n_generated_dev : 0;
+    const int step_s = p.step_dev ? *p.step_dev : 0;
+    const RowKnobs kn = row_knobs(p, b);
+    const uint4* we = reinterpret_cast<const uint4*>(pw.warp + b);
+    const uint4 wa = we[0], wb = we[1];
+    const int n_gen = p.n_generated_dev ? n_gen_s - kn.origin : 0;      // the ROW's token count and step (sample_kernel)
+    const int n_hist = min(n_gen, p.gen_stride);
+    const uint32_t step = p.step_dev ? (uint32_t)(step_s - kn.origin) : 0u;
+    const int* gsrc = p.generated ? p.generated + (size_t)b * p.gen_stride + (tid < p.gen_stride ? tid : 0) : reinterpret_cast<const int*>(lg);
+    const int gtok0 = *gsrc;               // entry `tid` of the row's history (penalty and ban), requested before the count is known
+    float x[EPT];
+    unsigned char sup[EPT];
+#pragma unroll
+    for (int it = 0; it < EPT; ++it) {
+        const int v = it * 256 + tid;
+        x[it] = v < V ? lg[v] : -INFINITY;
+        sup[it] = (p.suppress_mask && v < V) ? p.suppress_mask[v] : (unsigned char)0;
+    }
+    if (done) return;
+    QTTS_TS_DRAINED(1);                    // (tstamp build: phases 1..5 = logits arrived | processors | cuts | drawn | rows gathered)
+    const float min_p = __uint_as_float(wa.x), typical_p = __uint_as_float(wa.y), eps_cut = __uint_as_float(wa.z), eta_cut = __uint_as_float(wa.w);
+    const int ngram = (int)wb.x;
+
+    int par = 0;                           // parity of the next block reduction (the partials' buffer)
+    auto bsum = [&](float v) -> float {
+        v = wave_sum64_dpp(v);
+        if (lane == 0) fred[par * 4 + wave] = v;
+        __syncthreads();
+        const float r = (fred[par * 4 + 0] + fred[par * 4 + 1]) + (fred[par * 4 + 2] + fred[par * 4 + 3]);
+        par ^= 1;
+        return r;
+    };
+    auto bmax = [&](float v) -> float {
+        v = wave_max64_dpp(v);
+        if (lane == 0) fred[par * 4 + wave] = v;
+        __syncthreads();
+        const float r = fmaxf(fmaxf(fred[par * 4 + 0], fred[par * 4 + 1]), fmaxf(fred[par * 4 + 2], fred[par * 4 + 3]));
+        par ^= 1;
+        return r;
+    };
+
+    // ---- 1. RepetitionPenalty and NoRepeatNGram: both are scatters over the row's history -> flags in LDS
+    const bool want_rep = p.generated && kn.rep != 1.0f;
+    const bool want_ban = p.generated && ngram > 0 && n_hist >= ngram;     // (fewer than n tokens: no n-gram exists yet)
+    if (want_rep || want_ban) {
+#pragma unroll
+        for (int it = 0; it < EPT; ++it) { sc[it * 256 + tid] = 0.f; ban[it * 256 + tid] = 0; }
+        __syncthreads();
+        const int* h = p.generated + (size_t)b * p.gen_stride;
+        if (want_rep) {
+            if (tid < n_hist && gtok0 >= 0 && gtok0 < V) sc[gtok0] = 1.f;          // entries 0..255: prefetched at entry
+            for (int i = tid + 256; i < n_hist; i += 256) {
+                const int tok = h[i];
+                if (tok >= 0 && tok < V) sc[tok] = 1.f;
+            }
+        }
+        if (want_ban) {
+            // h[i + n - 1] is banned for every i <= c - n whose n - 1 tokens h[i ..] equal the last n - 1 tokens (n = 1: every token)
+            const int np = ngram - 1;
+            const int* suf = h + (n_hist - np);
+            for (int i = tid; i <= n_hist - ngram; i += 256) {
+                bool match = true;
+                for (int j = 0; j < np && match; ++j) {
+                    const int a = (j == 0 && i == tid) ? gtok0 : h[i + j];
+                    match = a == suf[j];
+                }
+                if (match) {
+                    const int tok = (np == 0 && i == tid) ? gtok0 : h[i + np];
+                    if (tok >= 0 && tok < V) ban[tok] = 1;
+                }
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int it = 0; it < EPT; ++it) {
+            const int v = it * 256 + tid;
+            if (want_rep && sc[v] != 0.f) x[it] = x[it] < 0.f ? x[it] * kn.rep : x[it] / kn.rep;
+            if (ban[v]) x[it] = -INFINITY;
+        }
+        __syncthreads();                                     // flags consumed before `sc` is written again
+    }
+    // ---- 2. MinNewTokensLength, SuppressTokens
+    const bool block_eos = p.eos >= 0 && n_gen < kn.min_new;
+#pragma unroll
+    for (int it = 0; it < EPT; ++it) {
+        const int v = it * 256 + tid;
+        if ((block_eos && v == p.eos) || sup[it]) x[it] = -INFINITY;
+    }
+    QTTS_TS(2);
+
+    int token = 0;
+    if (!kn.do_sample) {
+        // ---- greedy: argmax, ties towards the lowest index (torch.argmax)
+        float bv = -INFINITY;
+        int bi = 0x7fffffff;
+#pragma unroll
+        for (int it = 0; it < EPT; ++it) {
+            const int v = it * 256 + tid;
+            if (v < V && (x[it] > bv || (x[it] == bv && v < bi))) { bv = x[it]; bi = v; }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const float ov = __shfl_xor(bv, o);
+            const int oi = __shfl_xor(bi, o);
+            if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+        }
+        if (lane == 0) { fred[wave] = bv; ired[wave] = bi; }
+        __syncthreads();
+        bv = fred[0]; bi = ired[0];
+        for (int w = 1; w < 4; ++w)
+            if (fred[w] > bv || (fred[w] == bv && ired[w] < bi)) { bv = fred[w]; bi = ired[w]; }
+        token = bi;
+    } else {
+        uint32_t rnd[4];
+        philox4x32_10(step, kn.ctr_row, p.stream_id, 0u, (uint32_t)kn.seed, (uint32_t)(kn.seed >> 32), rnd);
+        const float u = (float)(rnd[0] >> 8) * (1.0f / 16777216.0f);
+        // ---- 3. Temperature; the keys of the scores (TopK and TopP cut on them)
+        uint32_t kx[EPT];
+#pragma unroll
+        for (int it = 0; it < EPT; ++it) {
+            if (kn.temperature != 1.0f) x[it] = x[it] / kn.temperature;
+            kx[it] = it * 256 + tid < V ? float_key(x[it]) : 0u;
+        }
+        // ---- 4. TopK: the k-th largest key = the largest value with #{key >= value} >= k; HF keeps every score >= it (ties included)
+        if (kn.top_k > 0 && kn.top_k < V) {
+            uint32_t prefix = 0u;
+#pragma unroll 1
+            for (int bit = 31; bit >= 0; --bit) {
+                const uint32_t cand = prefix | (1u << bit);
+                int cnt = 0;
+#pragma unroll
+                for (int it = 0; it < EPT; ++it) cnt += __popcll(__ballot(kx[it] >= cand));
+                if (lane == 0) ired[par * 4 + wave] = cnt;
+                __syncthreads();
+                if ((ired[par * 4 + 0] + ired[par * 4 + 1]) + (ired[par * 4 + 2] + ired[par * 4 + 3]) >= kn.top_k) prefix = cand;
+                par ^= 1;
+            }
+#pragma unroll
+            for (int it = 0; it < EPT; ++it)
+                if (kx[it] < prefix) x[it] = -INFINITY;
+        }
+        // softmax numerators of the scores as they stand: m = max, e = exp(x - m) (0 for removed tokens), Z = sum
+        float m, Z;
+        float e[EPT];
+        auto renorm = [&]() {
+            float tm = -INFINITY;
+#pragma unroll
+            for (int it = 0; it < EPT; ++it) tm = fmaxf(tm, x[it]);
+            m = bmax(tm);
+            float s = 0.f;
+#pragma unroll
+            for (int it = 0; it < EPT; ++it) {
+                e[it] = x[it] == -INFINITY ? 0.f : expf(x[it] - m);
+                s += e[it];
+            }
+            Z = bsum(s);
+        };
+        auto resum = [&]() {
+            float s = 0.f;
+#pragma unroll
+            for (int it = 0; it < EPT; ++it) s += e[it];
+            Z = bsum(s);
+        };
+        // H = -sum p log p over the finite entries, with log p = (x - m) - log Z
+        auto entropy = [&]() -> float {
+            const float logZ = logf(Z);
+            float s = 0.f;
+#pragma unroll
+            for (int it = 0; it < EPT; ++it)
+                if (e[it] > 0.f) s += e[it] * ((x[it] - m) - logZ);
+            return -bsum(s) / Z;
+        };
+        renorm();
+        // ---- 5. TopP: a token stays iff the mass of everything ranked strictly above it is < top_p (sample_kernel's general top-p)
+        if (kn.top_p < 1.0f) {
+            const float P = kn.top_p * Z;
+            uint32_t cut = 0u;                               // largest key whose strictly-above mass is still >= P
+            bool any_cut = false;
+#pragma unroll 1
+            for (int bit = 31; bit >= 0; --bit) {
+                const uint32_t cand = cut | (1u << bit);
+                float above = 0.f;
+#pragma unroll
+                for (int it = 0; it < EPT; ++it) above += kx[it] > cand ? e[it] : 0.f;
+                if (bsum(above) >= P) { cut = cand; any_cut = true; }
+            }
+            if (any_cut) {
+#pragma unroll
+                for (int it = 0; it < EPT; ++it)
+                    if (kx[it] <= cut) { x[it] = -INFINITY; e[it] = 0.f; }
+            }
+            resum();
+        }
+        // ---- 6. MinP: p < min_p * max(p)  <=>  e < min_p (the maximum has e = 1)
+        if (min_p > 0.f) {
+#pragma unroll
+            for (int it = 0; it < EPT; ++it)
+                if (e[it] < min_p && x[it] != m) { x[it] = -INFINITY; e[it] = 0.f; }
+            resum();
+        }
+        // ---- 7. Typical: d = |-log p - H|; keep d <= t*, the smallest d whose group {d <= t*} holds mass >= typical_p (never reached:
+        // keep all).  t* = the largest key c with mass{key(d) < c} < typical_p * Z; d >= 0, so float_key orders it.
+        if (typical_p > 0.f && typical_p < 1.0f) {
+            const float H = entropy();
+            const float logZ = logf(Z);
+#pragma unroll
+            for (int it = 0; it < EPT; ++it)
+                kx[it] = x[it] == -INFINITY ? 0xffffffffu : float_key(fabsf(-((x[it] - m) - logZ) - H));
+            const float target = typical_p * Z;
+            uint32_t c = 0u;
+#pragma unroll 1
+            for (int bit = 31; bit >= 0; --bit) {
+                const uint32_t cand = c | (1u << bit);
+                float below = 0.f;
+#pragma unroll
+                for (int it = 0; it < EPT; ++it) below += kx[it] < cand ? e[it] : 0.f;
+                if (bsum(below) < target) c = cand;
+            }
+#pragma unroll
+            for (int it = 0; it < EPT; ++it)
+                if (kx[it] > c) x[it] = -INFINITY;
+            renorm();                                        // (the one cut that can remove the maximum)
+        }
+        // ---- 8. EpsilonCutoff: p < eps, except scores equal to the maximum
+        if (eps_cut > 0.f && eps_cut < 1.0f) {
+            const float thr = eps_cut * Z;
+#pragma unroll
+            for (int it = 0; it < EPT; ++it)
+                if (e[it] < thr && x[it] != m) { x[it] = -INFINITY; e[it] = 0.f; }
+            resum();
+        }
+        // ---- 9. EtaCutoff: p < min(eps, sqrt(eps) * exp(-H)), except scores equal to the maximum
+        if (eta_cut > 0.f && eta_cut < 1.0f) {
+            const float H = entropy();
+            const float thr = fminf(eta_cut, sqrtf(eta_cut) * expf(-H)) * Z;
+#pragma unroll
+            for (int it = 0; it < EPT; ++it)
+                if (e[it] < thr && x[it] != m) { x[it] = -INFINITY; e[it] = 0.f; }
+            resum();
+        }
+        QTTS_TS(3);
+        // ---- 10. inverse CDF, in sample_kernel's scan order for this row's top_k
+        if (kn.top_k > 0 && kn.top_k <= 256 && kn.top_k < V) {
+            // slot order (wave, slice, lane): wave totals first, then every wave scans its own slices behind the waves before it
+            float run = 0.f;
+#pragma unroll
+            for (int it = 0; it < EPT; ++it) run += lane_bcast(wave_incl_scan64_dpp(e[it], lane), 63);
+            if (lane == 0) fred[par * 4 + wave] = run;
+            __syncthreads();
+            const float w0 = fred[par * 4 + 0], w1 = fred[par * 4 + 1], w2 = fred[par * 4 + 2], w3 = fred[par * 4 + 3];
+            par ^= 1;
+            const float target = u * (((w0 + w1) + w2) + w3);
+            run = wave == 0 ? 0.f : (wave == 1 ? w0 : (wave == 2 ? w0 + w1 : (w0 + w1) + w2));
+            int pick = -1, last = -1;
+#pragma unroll
+            for (int it = 0; it < EPT; ++it) {
+                const float inc = wave_incl_scan64_dpp(e[it], lane);
+                const unsigned long long nz = __ballot(e[it] > 0.f);
+                if (nz) last = it * 256 + wave * 64 + 63 - __clzll((long long)nz);
+                const unsigned long long hit = __ballot(e[it] > 0.f && run + inc > target);
+                if (hit && pick < 0) pick = it * 256 + wave * 64 + __ffsll((long long)hit) - 1;
+                run += lane_bcast(inc, 63);
+            }
+            if (lane == 0) { wpick[wave] = pick; wlast[wave] = last; }
+            __syncthreads();
+            token = -1;
+            for (int w = 3; w >= 0; --w)
+                if (wpick[w] >= 0) token = wpick[w];
+            if (token < 0)                                   // rounding at the very top of the CDF: the last token with mass
+                for (int w = 0; w < 4; ++w)
+                    if (wlast[w] >= 0) token = wlast[w];
+        } else {
+            // index order: sample_kernel's general path on the numerators
+#pragma unroll
+            for (int it = 0; it < EPT; ++it) sc[it * 256 + tid] = e[it];
+            if (tid == 0) { pick_lo = 0x7fffffff; pick_hi = -1; }
+            __syncthreads();
+            const int chunk = (V + 255) / 256;
+            const int v0 = tid * chunk, v1 = min(V, v0 + chunk);
+            float mine = 0.f;
+            for (int v = v0; v < v1; ++v) mine += sc[v];
+            scan[tid] = mine;
+            __syncthreads();
+            for (int o = 1; o < 256; o <<= 1) {              // inclusive Hillis-Steele scan in index order
+                const float add = tid >= o ? scan[tid - o] : 0.f;
+                __syncthreads();
+                scan[tid] += add;
+                __syncthreads();
+            }
+            const float target = u * scan[255];
+            float run = scan[tid] - mine;
+            for (int v = v0; v < v1; ++v) {
+                const float ev = sc[v];
+                if (ev > 0.f) {
+                    atomicMax(&pick_hi, v);
+                    if (run + ev > target) { atomicMin(&pick_lo, v); break; }
+                }
+                run += ev;
+            }
+            __syncthreads();
+            token = pick_lo != 0x7fffffff ? pick_lo : pick_hi;
+        }
+    }
+    QTTS_TS(4);
+
+    if (token < 0 || token >= V) token = 0;   // no finite score left, or NaN logits: never an out-of-range gather index
+    gather_next_rows(p, token, b, tid);
+    if (tid == 0) finish_row(p, b, n_gen, kn.limit, token);
+    QTTS_TS_DRAINED(5);
+    QTTS_TS_END(sample, 3, V, 1);
+}
+
+void launch_sample_warp(const SampleWarpParams& p, hipStream_t st) {
+    QTTS_REQUIRE(p.s.V <= SAMPLE_MAX_V, QTTS_ERR_LIMIT, "sample: vocab too large");
+    QTTS_REQUIRE(p.s.rows && !p.s.rows_sub && p.warp, QTTS_ERR_ARG, "sample_warp: the talker's launch of a per-row table only");
+    if (p.s.V <= 2048) hipLaunchKernelGGL(sample_warp_kernel<8>, dim3(p.s.B), dim3(256), 0, st, p);
+    else if (p.s.V <= 3072) hipLaunchKernelGGL(sample_warp_kernel<12>, dim3(p.s.B), dim3(256), 0, st, p);
+    else if (p.s.V <= 4096) hipLaunchKernelGGL(sample_warp_kernel<16>, dim3(p.s.B), dim3(256), 0, st, p);
+    else hipLaunchKernelGGL(sample_warp_kernel<32>, dim3(p.s.B), dim3(256), 0, st, p);
+    QTTS_CHECK_HIP(hipGetLastError());
+}
+
 // ---------------------------------------------------------------------------------- loop bookkeeping
 // After every row sampled token #n: n_generated++, kv_len++, and latch `done` exactly where HF's
 // stopping criteria would break (all rows finished, or max_new_tokens reached).  With per-row positions (st.row_len) the rows

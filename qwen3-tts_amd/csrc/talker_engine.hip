@@ -100,13 +100,14 @@ struct qtts_talker {
         float top_p, temperature, rep, sub_top_p, sub_temperature;
         const void *codes, *hidden, *trailing, *tts_pad, *generated;
         int row_mode, row_fast_t, row_fast_c, row_pos;
+        int row_warp_t;             // the talker's sampler of the table is sample_warp_kernel (a row uses a qtts_row_warpers knob)
         bool operator==(const GraphKey& o) const { return memcmp(this, &o, sizeof(GraphKey)) == 0; }
     } graph_key;
     GraphKey make_key(const qtts_sampling& sp, int eos, int min_new, int max_new, int max_frames, const void* codes, const void* hidden) const {
         GraphKey key;
         memset(&key, 0, sizeof(key));          // (padding bytes take part in the comparison)
         key.B = B; key.Tt = Tt; key.eos = eos; key.max_new = max_new; key.max_frames = max_frames;
-        if (row_mode) { key.row_mode = 1; key.row_fast_t = row_fast_t; key.row_fast_c = row_fast_c; }
+        if (row_mode) { key.row_mode = 1; key.row_fast_t = row_fast_t; key.row_fast_c = row_fast_c; key.row_warp_t = row_warp_t; }
         else {
             key.min_new = min_new; key.do_sample = sp.do_sample; key.top_k = sp.top_k; key.sub_do_sample = sp.subtalker_dosample;
             key.sub_top_k = sp.subtalker_top_k; key.top_p = sp.top_p; key.temperature = sp.temperature; key.rep = sp.repetition_penalty;
@@ -120,6 +121,13 @@ struct qtts_talker {
     // per-row settings (qtts_talker_generate_rows / stream_begin_rows): max_batch entries, uploaded per call like seed_d
     DevBuf rows_d;
     bool row_mode = false, row_fast_t = false, row_fast_c = false;
+    // the rows' remaining warpers (qtts_talker_set_row_warpers): a second table of max_batch 32-byte entries, uploaded with the rows it
+    // belongs to.  `row_warp_t`: some row of the table has one of them on -- the talker's sampler is then sample_warp_kernel; like
+    // row_fast_t it is part of the graph key and monotone within a stream.  `warp_pending`: the table the NEXT table call consumes.
+    DevBuf warp_d;
+    bool row_warp_t = false;
+    std::vector<RowWarpers> warp_pending;
+    bool warp_pending_set = false;
     int64_t graph_captures = 0;        // frame-graph captures over the engine's life
     // resumable generation (qtts_talker_stream_*): everything a later call needs to keep stepping the same request
     struct StreamGen {
@@ -134,6 +142,7 @@ struct qtts_talker {
         bool admitting = false;
         int max_row = 0;
         std::vector<SampleRow> tab;
+        std::vector<RowWarpers> wtab;  // ... and of the warper table
         hipStream_t st = nullptr;
     } sg;
     int64_t admit_calls = 0, admitted_rows = 0;      // of the last stream
@@ -1038,7 +1047,7 @@ void qtts_talker::finalize() {
         cp_hid.alloc((size_t)CP_HID_SLOTS * 8 * (bf16 ? cd.H / 2 : cd.H) * 8);
         QTTS_CHECK_HIP(hipMemset(cp_hid.p, 0, cp_hid.bytes));
     }
-    n_pad_d.alloc(R * 4); suppress.alloc(c.vocab_size); seed_d.alloc(8); rows_d.alloc((size_t)R * sizeof(SampleRow));
+    n_pad_d.alloc(R * 4); suppress.alloc(c.vocab_size); seed_d.alloc(8); rows_d.alloc((size_t)R * sizeof(SampleRow)); warp_d.alloc((size_t)R * sizeof(RowWarpers));
     QTTS_CHECK_HIP(hipMemset(ss_rows.p, 0, ss_rows.bytes));
     int* ip = ints.as<int>();
     row_len_p = ip + 64 + 64;
@@ -1182,7 +1191,8 @@ void qtts_talker::sample_talker(const qtts_sampling& sp, int eos, int min_new, i
     p.max_new_tokens = max_new; p.done_in = ss.done;
     if (row_mode) { p.rows = rows_d.as<SampleRow>(); p.rows_sub = 0; p.rows_fast = row_fast_t; }
     if (tf.codes && tf.trace) launch_teacher(teacher_params(), 0, st);
-    launch_sample(p, st);
+    if (row_mode && row_warp_t) { SampleWarpParams pw{p, warp_d.as<RowWarpers>()}; launch_sample_warp(pw, st); }
+    else launch_sample(p, st);
     launch_sample_finish(ss, B, max_new, st);
     if (tf.codes) launch_teacher(teacher_params(), 1, st);
 }
@@ -1428,7 +1438,45 @@ struct RowTable {
     int max_new = 0;            // the largest limit: buffer sizes, the stop latch, the frame count's bound
     int poll_from = 0x7fffffff; // no row can finish before this many tokens exist (EOS blocked and limit not reached): no poll needed earlier
     bool fast_t = true, fast_c = true;      // every row meets sample_kernel_v2's predicate, talker / subtalker half (launch_sample)
+    std::vector<RowWarpers> wtab;           // the rows' warpers (all off without a pending qtts_talker_set_row_warpers table)
+    bool warp = false;                      // some row has one on: the talker's sampler is sample_warp_kernel
 };
+// one request's warpers, checked, as sample_warp_kernel reads them (`b`: the row the messages name); typical_p = 1 is stored as off
+static RowWarpers check_warpers(const qtts_row_warpers& q, int b, const char* who) {
+    auto fail = [&](const char* what) { throw Error(QTTS_ERR_ARG, std::string(who) + ": row " + std::to_string(b) + ": " + what); };
+    if (!(q.min_p >= 0.0f && q.min_p <= 1.0f)) fail("min_p must be in [0, 1]");
+    if (!(q.typical_p >= 0.0f && q.typical_p <= 1.0f)) fail("typical_p must be in [0, 1]");
+    if (!(q.epsilon_cutoff >= 0.0f && q.epsilon_cutoff < 1.0f)) fail("epsilon_cutoff must be in [0, 1)");
+    if (!(q.eta_cutoff >= 0.0f && q.eta_cutoff < 1.0f)) fail("eta_cutoff must be in [0, 1)");
+    if (q.no_repeat_ngram_size < 0) fail("no_repeat_ngram_size >= 0");
+    RowWarpers o;
+    memset(&o, 0, sizeof(o));
+    o.min_p = q.min_p; o.typical_p = q.typical_p < 1.0f ? q.typical_p : 0.0f; o.epsilon_cutoff = q.epsilon_cutoff; o.eta_cutoff = q.eta_cutoff;
+    o.no_repeat_ngram_size = q.no_repeat_ngram_size;
+    return o;
+}
+static bool warpers_on(const RowWarpers& o) {
+    return o.min_p > 0.0f || o.typical_p > 0.0f || o.epsilon_cutoff > 0.0f || o.eta_cutoff > 0.0f || o.no_repeat_ngram_size > 0;
+}
+// The pending warper table, taken by the call that consumes it (one-shot: whatever the call does next, the table is gone).  Empty: no
+// table was set.  A count other than the call's is refused before the call has changed anything.
+static std::vector<RowWarpers> take_warpers(qtts_talker* t, int n, const char* who) {
+    std::vector<RowWarpers> w;
+    if (!t->warp_pending_set) return w;
+    w.swap(t->warp_pending);
+    t->warp_pending_set = false;
+    if ((int)w.size() != n)
+        throw Error(QTTS_ERR_ARG, std::string(who) + ": the pending warper table (qtts_talker_set_row_warpers) has " + std::to_string(w.size()) +
+                                      " rows, this call " + std::to_string(n));
+    return w;
+}
+// a scalar call cannot consume a table: refused, and the table is dropped
+static void refuse_pending_warpers(qtts_talker* t, const char* who) {
+    if (!t->warp_pending_set) return;
+    t->warp_pending.clear();
+    t->warp_pending_set = false;
+    throw Error(QTTS_ERR_ARG, std::string(who) + ": a warper table is pending (qtts_talker_set_row_warpers); it belongs to a per-row table call");
+}
 // one request's settings, checked, as the samplers read them (`b`: the row the messages name)
 static SampleRow check_row(const qtts_row_sampling& q, int b, const char* who) {
     auto fail = [&](int code, int b, const char* what) { throw Error(code, std::string(who) + ": row " + std::to_string(b) + ": " + what); };
@@ -1450,14 +1498,17 @@ static SampleRow check_row(const qtts_row_sampling& q, int b, const char* who) {
 // whether a row meets sample_kernel_v2's predicate, talker / subtalker half (launch_sample)
 static bool row_fast_talker(const SampleRow& o, int V) { return o.do_sample && o.top_k > 0 && o.top_k <= 64 && o.top_k < V && V <= 4096; }
 static bool row_fast_sub(const SampleRow& o, int Vc) { return o.sub_do_sample && o.sub_top_k > 0 && o.sub_top_k <= 64 && o.sub_top_k < Vc && Vc <= 4096; }
-static RowTable check_rows(const qtts_talker* t, const qtts_row_sampling* rows, int n_rows, const char* who) {
+static RowTable check_rows(qtts_talker* t, const qtts_row_sampling* rows, int n_rows, const char* who) {
     QTTS_REQUIRE(rows, QTTS_ERR_ARG, "null argument");
+    std::vector<RowWarpers> w = take_warpers(t, n_rows, who);
     QTTS_REQUIRE(n_rows == t->B, QTTS_ERR_ARG, std::string(who) + ": n_rows (" + std::to_string(n_rows) + ") must equal the prefilled batch (" +
                                                    std::to_string(t->B) + ")");
     QTTS_REQUIRE(!t->tf.codes, QTTS_ERR_ARG, std::string(who) + ": teacher forcing takes scalar settings (qtts_talker_generate), not a per-row table");
     QTTS_REQUIRE(t->profile != 2, QTTS_ERR_ARG, std::string(who) + ": profile mode 2 takes scalar settings, not a per-row table");
     RowTable r;
     r.tab.resize(n_rows);
+    r.wtab.assign(n_rows, RowWarpers{});
+    for (int b = 0; b < n_rows && !w.empty(); ++b) { r.wtab[b] = w[b]; r.warp = r.warp || warpers_on(w[b]); }
     const int V = t->cfg.vocab_size, Vc = t->cfg.cp_vocab_size;
     for (int b = 0; b < n_rows; ++b) {
         const qtts_row_sampling& q = rows[b];
@@ -1483,6 +1534,8 @@ void qtts_talker::admit(int n_new, const int32_t* rows_host, const float* embeds
                         const qtts_row_sampling* settings, hipStream_t st) {
     const char* who = "stream_admit";
     auto& g = sg;
+    std::vector<RowWarpers> wnew = take_warpers(this, n_new, who);
+    if (wnew.empty()) wnew.assign(std::max(n_new, 0), RowWarpers{});
     auto fail = [&](int code, int b, const std::string& what) { throw Error(code, std::string(who) + ": row " + std::to_string(b) + ": " + what); };
     QTTS_REQUIRE(n_new >= 1 && n_new <= B, QTTS_ERR_ARG, "stream_admit: 1 <= n_new <= the stream's rows");
     QTTS_REQUIRE(T >= 1 && Tt_ >= 1, QTTS_ERR_ARG, "stream_admit: T >= 1 and >= 1 trailing row");
@@ -1539,6 +1592,13 @@ void qtts_talker::admit(int n_new, const int32_t* rows_host, const float* embeds
         destroy_graph(); graph_nodes = 0;
         graph_key.row_fast_t = row_fast_t; graph_key.row_fast_c = row_fast_c;
     }
+    bool warp_t = row_warp_t;                                // monotone like the classes above: the first warper of a stream re-captures once
+    for (auto& e : wnew) warp_t = warp_t || warpers_on(e);
+    if (warp_t != row_warp_t) {
+        row_warp_t = warp_t;
+        destroy_graph(); graph_nodes = 0;
+        graph_key.row_warp_t = 1;
+    }
     if (pooled() && row_pos) {
         for (int i = 0; i < n_new; ++i) pool_release(rows_host[i]);
         for (int i = 0; i < n_new; ++i) pool_grant(rows_host[i], cdiv(T, 16));
@@ -1572,6 +1632,7 @@ void qtts_talker::admit(int n_new, const int32_t* rows_host, const float* embeds
             QTTS_CHECK_HIP(hipMemcpyAsync(tr + (size_t)j * H, tts_pad.p, (size_t)H * 4, hipMemcpyDeviceToDevice, st));
         QTTS_CHECK_HIP(hipMemcpyAsync(n_pad_d.as<int>() + b, &npad_g[i], 4, hipMemcpyHostToDevice, st));
         QTTS_CHECK_HIP(hipMemcpyAsync(rows_d.as<SampleRow>() + b, &entries[i], sizeof(SampleRow), hipMemcpyHostToDevice, st));
+        QTTS_CHECK_HIP(hipMemcpyAsync(warp_d.as<RowWarpers>() + b, &wnew[i], sizeof(RowWarpers), hipMemcpyHostToDevice, st));
         QTTS_CHECK_HIP(hipMemcpyAsync(ss.unfinished + b, &one, 4, hipMemcpyHostToDevice, st));
         if (row_pos) QTTS_CHECK_HIP(hipMemcpyAsync(row_len_p + b, &T, 4, hipMemcpyHostToDevice, st));
     }
@@ -1589,10 +1650,11 @@ void qtts_talker::admit(int n_new, const int32_t* rows_host, const float* embeds
         p.tok_out = cur_tok.as<int>() + b; p.tok_stride = 1; p.unfinished = ss.unfinished + b; p.generated_out = generated.as<int>() + (size_t)b * gen_cap;
         p.max_new_tokens = g.max_new; p.done_in = ss.done;
         p.rows = rows_d.as<SampleRow>() + b; p.rows_sub = 0; p.rows_fast = row_fast_t;
-        launch_sample(p, st);
+        if (row_warp_t) { SampleWarpParams pw{p, warp_d.as<RowWarpers>() + b}; launch_sample_warp(pw, st); }
+        else launch_sample(p, st);
     }
     QTTS_CHECK_HIP(hipStreamSynchronize(st));      // (host buffers above must outlive the copies)
-    for (int i = 0; i < n_new; ++i) g.tab[rows_host[i]] = entries[i];
+    for (int i = 0; i < n_new; ++i) { g.tab[rows_host[i]] = entries[i]; g.wtab[rows_host[i]] = wnew[i]; }
     if (row_pos) mirror_rows(st);
     g.done = 0;
     admit_calls += 1; admitted_rows += n_new;
@@ -1609,12 +1671,13 @@ static void upload_call_state(qtts_talker* t, const qtts_sampling& sp, const Row
         QTTS_REQUIRE(suppress_host[i] >= 0 && suppress_host[i] < V, QTTS_ERR_ARG, "suppress token out of range");
         m[suppress_host[i]] = 1;
     }
-    t->row_mode = rt != nullptr; t->row_fast_t = rt && rt->fast_t; t->row_fast_c = rt && rt->fast_c;
+    t->row_mode = rt != nullptr; t->row_fast_t = rt && rt->fast_t; t->row_fast_c = rt && rt->fast_c; t->row_warp_t = rt && rt->warp;
     t->row_pos = false; t->ss.row_len = nullptr;       // (per-row positions are a mode of ONE stream: stream_begin_body sets it after this)
     QTTS_CHECK_HIP(hipMemcpyAsync(t->suppress.p, m.data(), V, hipMemcpyHostToDevice, st));
     const unsigned long long seed = sp.seed;
     QTTS_CHECK_HIP(hipMemcpyAsync(t->seed_d.p, &seed, 8, hipMemcpyHostToDevice, st));
     if (rt) QTTS_CHECK_HIP(hipMemcpyAsync(t->rows_d.p, rt->tab.data(), rt->tab.size() * sizeof(SampleRow), hipMemcpyHostToDevice, st));
+    if (rt) QTTS_CHECK_HIP(hipMemcpyAsync(t->warp_d.p, rt->wtab.data(), rt->wtab.size() * sizeof(RowWarpers), hipMemcpyHostToDevice, st));
     QTTS_CHECK_HIP(hipStreamSynchronize(st));
     t->gen_cap = max_new;
     t->generated.ensure((size_t)t->B * max_new * 4);
@@ -1725,6 +1788,7 @@ int qtts_talker_generate(qtts_talker* t, const qtts_sampling* sp, int32_t max_ne
                          float* hidden_dev, int64_t* tokens_dev, int32_t* n_frames_host, void* stream) {
     QTTS_API_BEGIN
     QTTS_REQUIRE(t && sp && codes_dev && n_frames_host, QTTS_ERR_ARG, "null argument");
+    refuse_pending_warpers(t, "generate");
     QTTS_REQUIRE(t->prefilled, QTTS_ERR_STATE, "generate: prefill() first");
     QTTS_REQUIRE(max_new_tokens >= 1, QTTS_ERR_ARG, "max_new_tokens >= 1");
     QTTS_REQUIRE(t->T0 + max_new_tokens <= t->cfg.max_seq, QTTS_ERR_LIMIT, "prompt + max_new_tokens exceeds max_seq");
@@ -1807,7 +1871,7 @@ static void stream_begin_body(qtts_talker* t, const qtts_sampling* sp, const Row
     g.max_frames = std::max(1, max_new_tokens - 1); g.codes = codes_dev; g.hidden = hidden_dev;
     g.total = max_new_tokens - 1; g.st = st;
     if (max_row > 0) {
-        g.admitting = true; g.max_row = max_row; g.tab = rt->tab;
+        g.admitting = true; g.max_row = max_row; g.tab = rt->tab; g.wtab = rt->wtab;
         g.max_new = t->cfg.max_seq; g.max_frames = std::max(1, max_row - 1); g.total = t->cfg.max_seq - t->T0 - 1;
         // per-row positions: rows restart at their own prompt's length, so neither the step count nor the positions bound the stream --
         // its stop latch is "no row unfinished" alone
@@ -1831,6 +1895,7 @@ int qtts_talker_stream_begin(qtts_talker* t, const qtts_sampling* sp, int32_t ma
                              float* hidden_dev, void* stream) {
     QTTS_API_BEGIN
     QTTS_REQUIRE(t && sp && codes_dev, QTTS_ERR_ARG, "null argument");
+    refuse_pending_warpers(t, "stream_begin");
     QTTS_REQUIRE(t->prefilled, QTTS_ERR_STATE, "stream_begin: prefill() first");
     QTTS_REQUIRE(!t->profile, QTTS_ERR_STATE, "stream_begin: not available in profile mode");
     QTTS_REQUIRE(!t->tf.codes, QTTS_ERR_STATE, "stream_begin: teacher forcing is a qtts_talker_generate mode (clear it with set_teacher(NULL))");
@@ -1957,6 +2022,29 @@ int qtts_talker_stream_admit(qtts_talker* t, int32_t n_new, const int32_t* rows_
     QTTS_REQUIRE(t && rows_host && embeds_dev && n_pad_host && trailing_dev && settings_host, QTTS_ERR_ARG, "null argument");
     QTTS_REQUIRE(t->sg.active && t->sg.admitting, QTTS_ERR_STATE, "stream_admit: no admitting stream is open (qtts_talker_stream_begin_admitting first)");
     t->admit(n_new, rows_host, embeds_dev, T, n_pad_host, trailing_dev, Tt, settings_host, (hipStream_t)stream);
+    QTTS_API_END
+}
+
+int qtts_talker_set_row_warpers(qtts_talker* t, const qtts_row_warpers* rows_host, int32_t n_rows) {
+    QTTS_API_BEGIN
+    QTTS_REQUIRE(t, QTTS_ERR_ARG, "null handle");
+    t->warp_pending.clear();
+    t->warp_pending_set = false;
+    if (!rows_host || n_rows == 0) return 0;
+    QTTS_REQUIRE(n_rows >= 1 && n_rows <= t->cfg.max_batch, QTTS_ERR_ARG, "set_row_warpers: 1 <= n_rows <= max_batch");
+    std::vector<RowWarpers> w(n_rows);
+    for (int b = 0; b < n_rows; ++b) w[b] = check_warpers(rows_host[b], b, "set_row_warpers");
+    t->warp_pending.swap(w);
+    t->warp_pending_set = true;
+    QTTS_API_END
+}
+
+int qtts_talker_sampler_class(qtts_talker* t, int32_t* talker_host, int32_t* subtalker_host) {
+    QTTS_API_BEGIN
+    QTTS_REQUIRE(t && talker_host && subtalker_host, QTTS_ERR_ARG, "null argument");
+    const bool v2_t = t->cfg.vocab_size <= 4096, v2_c = t->cfg.cp_vocab_size <= 4096;
+    *talker_host = !t->row_mode ? 0 : (t->row_warp_t ? 3 : (t->row_fast_t && v2_t ? 1 : 2));
+    *subtalker_host = !t->row_mode ? 0 : (t->row_fast_c && v2_c ? 1 : 2);
     QTTS_API_END
 }
 

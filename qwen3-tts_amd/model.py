@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from .config import TalkerConfig
-from .talker import TalkerEngine
+from .talker import _WARP_ARGS, TalkerEngine
 
 
 @dataclass
@@ -291,18 +291,27 @@ class Qwen3TTSForConditionalGeneration:
         """Every sampling knob, `max_new_tokens` and the `seed` keyword take one value for the call (as the reference) or a sequence with
         one value per request; sequences are sliced per wave.  With a `seed` sequence each request keeps its own seed whichever wave
         and row it lands in, so a request's codes do not depend on what it was batched with.  With per-request knobs but ONE `seed` s,
-        request i samples with s + i; with no seed, every request draws a fresh one: requests never share their random draws."""
+        request i samples with s + i; with no seed, every request draws a fresh one: requests never share their random draws.
+        `min_p`, `typical_p`, `epsilon_cutoff`, `eta_cutoff` and `no_repeat_ngram_size` (keywords; the talker's codebook-0 sampler,
+        `TalkerEngine.generate`) are per call or per request alike, and put the call on per-request seeds.  Other unknown keywords are
+        still ignored."""
         c = self.config
         embeds, mask, trailing, pad = self.assemble_prompts(input_ids, languages, speakers, instruct_ids,
                                                             non_streaming_mode, ref_ids, voice_clone_prompt)
         suppress = [i for i in range(c.vocab_size - 1024, c.vocab_size) if i != c.codec_eos_token_id]      # M:2059-2063
         codes_all, hidden_all = [], []
         mb = self.talker.max_batch
-        from .talker import _fresh_seed, _is_row_seq
+        from .talker import _fresh_seed, _is_row_seq, _warp_table
         n_req = embeds.shape[0]
         knobs = dict(max_new_tokens=max_new_tokens, do_sample=do_sample, top_k=top_k, top_p=top_p, temperature=temperature,
                      subtalker_dosample=subtalker_dosample, subtalker_top_k=subtalker_top_k, subtalker_top_p=subtalker_top_p,
                      subtalker_temperature=subtalker_temperature, repetition_penalty=repetition_penalty)
+        # the warpers join the knobs only when some request has one ON under HF's gating (`_warp_table`): values that are off
+        # (`min_p=0`, `typical_p=1.0`) leave the call exactly where it is without them
+        warped = {k: kwargs[k] for k in _WARP_ARGS if kwargs.get(k) is not None}
+        if _warp_table(n_req, **warped) is None:
+            warped = {}
+        knobs.update(warped)
         seed = kwargs.get("seed")
         for k, v in list(knobs.items()) + [("seed", seed)]:
             if _is_row_seq(v) and len(v) != n_req:
@@ -322,7 +331,8 @@ class Qwen3TTSForConditionalGeneration:
                                        eos_token_id=eos_token_id if eos_token_id is not None else c.codec_eos_token_id,
                                        suppress_tokens=suppress, seed=seed, schedule=schedule, **knobs)
             return self._trim_at_eos(out, codes_all, hidden_all)
-        per_request = any(_is_row_seq(v) for v in knobs.values()) or _is_row_seq(seed)
+        # (a warper runs on the per-row table, whose Philox counter has no row term: every request then needs a seed of its own)
+        per_request = any(_is_row_seq(v) for v in knobs.values()) or _is_row_seq(seed) or bool(warped)
         if per_request:
             seeds = list(seed) if _is_row_seq(seed) else ([int(seed) + i for i in range(n_req)] if seed is not None else [None] * n_req)
         else:
@@ -383,7 +393,8 @@ class Qwen3TTSForConditionalGeneration:
                                                   subtalker_top_k=subtalker_top_k, subtalker_top_p=subtalker_top_p,
                                                   subtalker_temperature=subtalker_temperature, eos_token_id=eos,
                                                   repetition_penalty=repetition_penalty, suppress_tokens=suppress,
-                                                  seed=kwargs.get("seed"), schedule=schedule):
+                                                  seed=kwargs.get("seed"), schedule=schedule,
+                                                  **{k: kwargs[k] for k in _WARP_ARGS if kwargs.get(k) is not None}):
             if schedule != "waves":
                 yield packet
                 continue
@@ -542,6 +553,15 @@ class Qwen3TTSModel:
                 merged[k] = [default if v is None else v for v in user[k]]
             else:
                 merged[k] = user[k] if user[k] is not None else default
+        # HF generate's remaining sampling controls (forwarded to `model.generate()` by the reference): user value > generate_config.json
+        # > off; a None element of a per-request list takes what a None scalar would take
+        for k in _WARP_ARGS:
+            default = self.generate_defaults.get(k)
+            v = kwargs.get(k)
+            if isinstance(v, (list, tuple)):
+                merged[k] = [default if x is None else x for x in v]
+            elif v is not None or default is not None:
+                merged[k] = v if v is not None else default
         return merged
 
     def _unsupported(self, what: str):

@@ -107,6 +107,57 @@ _ROW_ARGS = ("do_sample", "top_k", "top_p", "temperature", "repetition_penalty",
              "subtalker_top_p", "subtalker_temperature", "max_new_tokens", "min_new_tokens", "seed")
 
 
+# the talker's remaining HF sampling controls (include/qtts.h `qtts_row_warpers`): per request like the knobs above, always on the table
+_WARP_ARGS = ("min_p", "typical_p", "epsilon_cutoff", "eta_cutoff", "no_repeat_ngram_size")
+
+
+def _resolve_row_warpers(min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None, no_repeat_ngram_size=None):
+    """One request's (min_p, typical_p, epsilon_cutoff, eta_cutoff, no_repeat_ngram_size) as the kernel takes them, 0 = off.  Gating is
+    transformers' `_get_logits_processor`: `min_p` None or 0 is off, `typical_p` None or >= 1 is off, the cutoffs act only for
+    0 < v < 1, `no_repeat_ngram_size` None or <= 0 is off.  Values HF's constructors refuse raise with HF's wording."""
+    mp = 0.0
+    if min_p is not None and min_p != 0:
+        mp = float(min_p)
+        if not 0.0 <= mp <= 1.0:
+            raise ValueError(f"`min_p` has to be a float in the [0, 1] interval, but is {min_p}")
+    tp = 0.0
+    if typical_p is not None and float(typical_p) < 1.0:
+        tp = float(typical_p)
+        if not tp > 0.0:
+            raise ValueError(f"`typical_p` has to be a float > 0 and < 1, but is {typical_p}")
+    cut = [float(v) if v is not None and 0.0 < float(v) < 1.0 else 0.0 for v in (epsilon_cutoff, eta_cutoff)]
+    n = 0
+    if no_repeat_ngram_size is not None:
+        n = _as_index(no_repeat_ngram_size)
+        if n is None:
+            raise ValueError(f"`ngram_size` has to be a strictly positive integer, but is {no_repeat_ngram_size}")
+        n = max(0, n)
+    return mp, tp, cut[0], cut[1], n
+
+
+def _warp_table(B: int, **kw):
+    """The warper table of a call (`_lib.RowWarpersC` x B) from the five `_WARP_ARGS`, each one value or a sequence of B; None when no
+    request has any of them on (the call is then exactly the call without them)."""
+    cols = {}
+    for k in _WARP_ARGS:
+        v = kw.get(k)
+        if _is_row_seq(v):
+            v = [_scalar(x) for x in v]
+            if len(v) != B:
+                raise ValueError(f"`{k}` has {len(v)} entries for a batch of {B} requests")
+        else:
+            v = [v] * B
+        cols[k] = v
+    rows = (_lib.RowWarpersC * B)()
+    on = False
+    for b in range(B):
+        vals = _resolve_row_warpers(**{k: cols[k][b] for k in _WARP_ARGS})
+        e = rows[b]
+        e.min_p, e.typical_p, e.epsilon_cutoff, e.eta_cutoff, e.no_repeat_ngram_size = vals
+        on = on or any(vals)
+    return rows if on else None
+
+
 def _is_row_seq(v) -> bool:
     """A per-request value list (list / tuple / 1-d array or tensor) as opposed to one value for the whole batch."""
     if isinstance(v, (list, tuple)):
@@ -248,13 +299,14 @@ class TalkerEngine:
             max_new_tokens = room
         return max_new_tokens
 
-    def _row_table(self, B: int, T: int, **kw):
+    def _row_table(self, B: int, T: int, force: bool = False, **kw):
         """The per-request settings table of a call (include/qtts.h `qtts_row_sampling`), or None when every argument of `_ROW_ARGS`
         is a scalar (the scalar path).  Any of them may be a sequence of length B; scalars are broadcast.  Every element goes through
         the checks a scalar goes through (`_check_warpers`, `_resolve_top`, `_clamp_new_tokens`).  Seeds: a `None` (the whole argument
         or one element) draws a fresh seed for each such row; ONE integer s gives request b the seed s + b, so that requests never share
-        their draws unless a seed list says so.  Returns (ctypes array of B entries, the largest max_new_tokens)."""
-        if not any(_is_row_seq(kw[k]) for k in _ROW_ARGS):
+        their draws unless a seed list says so.  `force`: the call has a warper table (`_warp_table`), which lives on the per-row table:
+        scalars are broadcast.  Returns (ctypes array of B entries, the largest max_new_tokens)."""
+        if not force and not any(_is_row_seq(kw[k]) for k in _ROW_ARGS):
             return None
         cols = {}
         for k in _ROW_ARGS:
@@ -362,7 +414,8 @@ class TalkerEngine:
                  repetition_penalty: float = 1.05, suppress_tokens: Optional[List[int]] = None,
                  output_hidden_states: bool = True, return_dict_in_generate: bool = True,
                  seed: Optional[int] = None, teacher_codes: Optional[torch.Tensor] = None,
-                 logit_steps: Optional[List[int]] = None, **unused) -> TalkerGenerateOutput:
+                 logit_steps: Optional[List[int]] = None, min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None,
+                 no_repeat_ngram_size=None, **unused) -> TalkerGenerateOutput:
         """`teacher_codes` (B, F, G) switches on the diagnostic teacher-forced mode (include/qtts.h `qtts_talker_set_teacher`):
         greedy, exactly F frames; the engine's own choices come back in `.own`, the raw cb-0 logits of the token steps listed in
         `logit_steps` in `.logits_trace`.
@@ -372,7 +425,13 @@ class TalkerEngine:
         values, one per request.  With any sequence the call runs on the engine's per-row table (`qtts_talker_generate_rows`): a
         request's draws then depend on its own seed only -- not on its row or on the other requests -- and changing the values between
         calls does not re-capture the frame graph.  Request b's frames are `codes[b]` up to its first eos in codebook 0; a request
-        that reached its own `max_new_tokens` m receives eos from `tokens[b, m - 1]` on (a scalar run keeps the sampled token there)."""
+        that reached its own `max_new_tokens` m receives eos from `tokens[b, m - 1]` on (a scalar run keeps the sampled token there).
+
+        `min_p`, `typical_p`, `epsilon_cutoff`, `eta_cutoff` and `no_repeat_ngram_size` (HF generate's remaining sampling controls, for
+        the codebook-0 sampler; gating and errors as in transformers, `_resolve_row_warpers`) are one value or a sequence of B as well.
+        Any of them that is on puts the call on the per-row table (scalars are broadcast; ONE integer seed s gives request b the seed
+        s + b) and the talker's sampler becomes `sample_warp_kernel` (`sampler_class()` reports 3).  Any OTHER keyword this signature
+        does not name is still swallowed."""
         c = self.config
         if inputs_embeds.dim() != 3 or inputs_embeds.shape[-1] != c.hidden_size:
             raise ValueError(f"inputs_embeds must be (B, T, {c.hidden_size})")
@@ -394,7 +453,9 @@ class TalkerEngine:
         expect = (torch.arange(T)[None, :] >= n_pad[:, None]).long()
         if not torch.equal(mask, expect) or int(n_pad.max()) >= T:
             raise ValueError("attention_mask must be left-padded: [0]*n_pad + [1]*(T-n_pad) per row")
-        table = self._row_table(B, T, do_sample=do_sample, top_k=top_k, top_p=top_p, temperature=temperature,
+        warp = _warp_table(B, min_p=min_p, typical_p=typical_p, epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff,
+                           no_repeat_ngram_size=no_repeat_ngram_size)
+        table = self._row_table(B, T, force=warp is not None, do_sample=do_sample, top_k=top_k, top_p=top_p, temperature=temperature,
                                 repetition_penalty=repetition_penalty, subtalker_dosample=subtalker_dosample,
                                 subtalker_top_k=subtalker_top_k, subtalker_top_p=subtalker_top_p,
                                 subtalker_temperature=subtalker_temperature, max_new_tokens=max_new_tokens,
@@ -467,6 +528,8 @@ class TalkerEngine:
                      C.c_void_p(tokens.data_ptr()), C.byref(n_frames), self._s())
             try:
                 if table is not None:
+                    if warp is not None:
+                        _lib.check(self._lib.qtts_talker_set_row_warpers(self._h, warp, B))
                     _lib.check(self._lib.qtts_talker_generate_rows(self._h, rows, B, eos, sup_c, len(suppress_tokens), *out_c))
                 else:
                     _lib.check(self._lib.qtts_talker_generate(self._h, C.byref(sp), int(max_new_tokens), int(min_new_tokens), eos,
@@ -486,7 +549,8 @@ class TalkerEngine:
                         subtalker_top_k: Optional[int] = 50, subtalker_top_p: Optional[float] = 1.0,
                         subtalker_temperature: Optional[float] = 0.9, eos_token_id: Optional[int] = None,
                         repetition_penalty: float = 1.05, suppress_tokens: Optional[List[int]] = None,
-                        seed: Optional[int] = None, schedule: str = "waves", **unused):
+                        seed: Optional[int] = None, schedule: str = "waves", min_p=None, typical_p=None, epsilon_cutoff=None,
+                        eta_cutoff=None, no_repeat_ngram_size=None, **unused):
         """Streaming OUTPUT (include/qtts.h `qtts_talker_stream_*`): a generator that yields `codes[:, f0:f1]` (B, k, G)
         int64 device tensors, k <= packet_frames, as the frames are produced; same arguments (per-request sequences included) and the
         same frames as `generate`.  Closing the generator early abandons the request.  Holds the engine lock while active.
@@ -502,7 +566,8 @@ class TalkerEngine:
                                            subtalker_top_k=subtalker_top_k, subtalker_top_p=subtalker_top_p,
                                            subtalker_temperature=subtalker_temperature, eos_token_id=eos_token_id,
                                            repetition_penalty=repetition_penalty, suppress_tokens=suppress_tokens, seed=seed,
-                                           row_positions=schedule == "continuous")
+                                           row_positions=schedule == "continuous", min_p=min_p, typical_p=typical_p,
+                                           epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff, no_repeat_ngram_size=no_repeat_ngram_size)
             return
         if schedule != "waves":
             raise ValueError(f"`schedule` must be 'waves', 'refill' or 'continuous', but is {schedule!r}")
@@ -522,7 +587,9 @@ class TalkerEngine:
         expect = (torch.arange(T)[None, :] >= n_pad[:, None]).long()
         if not torch.equal(mask, expect) or int(n_pad.max()) >= T:
             raise ValueError("attention_mask must be left-padded: [0]*n_pad + [1]*(T-n_pad) per row")
-        table = self._row_table(B, T, do_sample=do_sample, top_k=top_k, top_p=top_p, temperature=temperature,
+        warp = _warp_table(B, min_p=min_p, typical_p=typical_p, epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff,
+                           no_repeat_ngram_size=no_repeat_ngram_size)
+        table = self._row_table(B, T, force=warp is not None, do_sample=do_sample, top_k=top_k, top_p=top_p, temperature=temperature,
                                 repetition_penalty=repetition_penalty, subtalker_dosample=subtalker_dosample,
                                 subtalker_top_k=subtalker_top_k, subtalker_top_p=subtalker_top_p,
                                 subtalker_temperature=subtalker_temperature, max_new_tokens=max_new_tokens,
@@ -563,6 +630,8 @@ class TalkerEngine:
                                                          C.c_void_p(trail.data_ptr()), trail.shape[1],
                                                          C.c_void_p(pad.data_ptr()), self._s()))
                 if table is not None:
+                    if warp is not None:
+                        _lib.check(self._lib.qtts_talker_set_row_warpers(self._h, warp, B))
                     _lib.check(self._lib.qtts_talker_stream_begin_rows(self._h, rows, B, eos, sup_c, len(suppress_tokens),
                                                                        C.c_void_p(codes.data_ptr()), None, self._s()))
                 else:
@@ -587,12 +656,13 @@ class TalkerEngine:
     @_lib.locked
     def stream_open(self, inputs_embeds: torch.Tensor, n_pad: List[int], trailing_text_hidden: torch.Tensor, tts_pad_embed: torch.Tensor,
                     rows, max_row_tokens: int, eos_token_id: int, suppress_tokens: List[int], output_hidden_states: bool = False,
-                    row_positions: bool = False):
+                    row_positions: bool = False, warpers=None):
         """Prefill + `qtts_talker_stream_begin_admitting`: `rows` is a `_lib.RowSamplingC` array with one entry per row of
         `inputs_embeds` (B, T, H; row b left-padded by n_pad[b]).  Returns (codes (B, max_row_tokens - 1, G), hidden or None): the
         blocks the stream fills, ONE occupant per row at a time -- copy a finished row out before `stream_admit` re-uses it.
         `row_positions=True` opens the stream with `qtts_talker_stream_begin_admitting_rows`: every row carries its own KV length, an
-        admitted prompt restarts its row at its own length, and `stream_row_lens()` reads the lengths back."""
+        admitted prompt restarts its row at its own length, and `stream_row_lens()` reads the lengths back.  `warpers`: a
+        `_lib.RowWarpersC` array with one entry per row (`qtts_talker_set_row_warpers`), or None."""
         c, dev = self.config, self.device
         B, T, H = inputs_embeds.shape
         if B > self.max_batch:
@@ -611,6 +681,8 @@ class TalkerEngine:
             _lib.check(self._lib.qtts_talker_prefill(self._h, C.c_void_p(emb.data_ptr()), B, T, npad_c, C.c_void_p(trail.data_ptr()),
                                                      trail.shape[1], C.c_void_p(pad.data_ptr()), self._s()))
             begin = self._lib.qtts_talker_stream_begin_admitting_rows if row_positions else self._lib.qtts_talker_stream_begin_admitting
+            if warpers is not None:
+                _lib.check(self._lib.qtts_talker_set_row_warpers(self._h, warpers, B))
             _lib.check(begin(
                 self._h, rows, B, int(max_row_tokens), int(eos_token_id), sup_c, len(suppress_tokens), C.c_void_p(codes.data_ptr()),
                 C.c_void_p(hidden.data_ptr()) if hidden is not None else None, self._s()))
@@ -618,9 +690,10 @@ class TalkerEngine:
         return codes, hidden
 
     @_lib.locked
-    def stream_admit(self, row_ids: List[int], inputs_embeds: torch.Tensor, n_pad: List[int], trailing_text_hidden: torch.Tensor, rows):
+    def stream_admit(self, row_ids: List[int], inputs_embeds: torch.Tensor, n_pad: List[int], trailing_text_hidden: torch.Tensor, rows,
+                     warpers=None):
         """`qtts_talker_stream_admit`: request i of the group (inputs_embeds (n, T', H) left-padded by n_pad[i], trailing (n, Tt', H),
-        settings rows[i]) takes the finished row row_ids[i] of the open stream."""
+        settings rows[i], warpers[i] of a `_lib.RowWarpersC` array if given) takes the finished row row_ids[i] of the open stream."""
         dev = self.device
         n, T, H = inputs_embeds.shape
         emb = inputs_embeds.to(dev, torch.float32).contiguous()
@@ -629,6 +702,8 @@ class TalkerEngine:
         npad_c = (C.c_int32 * n)(*[int(x) for x in n_pad])
         self._stream.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.device(dev), torch.cuda.stream(self._stream):
+            if warpers is not None:
+                _lib.check(self._lib.qtts_talker_set_row_warpers(self._h, warpers, n))
             _lib.check(self._lib.qtts_talker_stream_admit(self._h, n, ids_c, C.c_void_p(emb.data_ptr()), T, npad_c,
                                                           C.c_void_p(trail.data_ptr()), trail.shape[1], rows, self._s()))
 
@@ -699,7 +774,8 @@ class TalkerEngine:
                        tts_pad_embed: torch.Tensor, max_new_tokens=2048, min_new_tokens=2, do_sample=True, top_k=50, top_p=1.0,
                        temperature=0.9, subtalker_dosample=True, subtalker_top_k=50, subtalker_top_p=1.0, subtalker_temperature=0.9,
                        eos_token_id: Optional[int] = None, repetition_penalty=1.05, suppress_tokens: Optional[List[int]] = None,
-                       output_hidden_states: bool = False, seed=None, packet_frames: int = 4, row_positions: bool = False, **unused):
+                       output_hidden_states: bool = False, seed=None, packet_frames: int = 4, row_positions: bool = False,
+                       min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None, no_repeat_ngram_size=None, **unused):
         """The refill schedule, packet by packet (`generate_stream(..., schedule="refill")`; `generate(..., schedule="refill")` collects
         what this yields): any number of requests on `max_batch` rows.  The rows start with the requests of the longest prompts; the
         stream runs in packets of `packet_frames` frames; after each packet every row whose occupant gained frames or finished is
@@ -751,6 +827,9 @@ class TalkerEngine:
                                   subtalker_top_k=subtalker_top_k, subtalker_top_p=subtalker_top_p,
                                   subtalker_temperature=subtalker_temperature, max_new_tokens=max_new_tokens,
                                   min_new_tokens=min_new_tokens, seed=seed)
+        # the requests' warpers (`_warp_table`; None: no request has any): a request keeps its entry through queueing, admission and restart
+        warps = _warp_table(N, min_p=min_p, typical_p=typical_p, epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff,
+                            no_repeat_ngram_size=no_repeat_ngram_size)
         for i in range(N):           # a request's limit inside the capacity its own prompt leaves (`_clamp_new_tokens`)
             rows[i].max_new_tokens = self._clamp_new_tokens(lens[i], int(rows[i].max_new_tokens))
         eos = c.codec_eos_token_id if eos_token_id is None else int(eos_token_id)
@@ -818,7 +897,8 @@ class TalkerEngine:
         def group(idx):
             Tg = max(lens[i] for i in idx)
             tab = (_lib.RowSamplingC * len(idx))(*[rows[i] for i in idx])
-            return emb[idx][:, T - Tg:], [Tg - lens[i] for i in idx], trail[idx], tab
+            wtab = (_lib.RowWarpersC * len(idx))(*[warps[i] for i in idx]) if warps is not None else None
+            return emb[idx][:, T - Tg:], [Tg - lens[i] for i in idx], trail[idx], tab, wtab
 
         with self._lock:
             caps0 = self.stats()["graph_captures"]
@@ -839,10 +919,11 @@ class TalkerEngine:
                             first = first[:width]
                             spare = min(spare, width - len(first))
                     queue = [i for i in queue if i not in first]
-                    e, npd, tr, tab = group(first + first[:1] * spare)
+                    e, npd, tr, tab, wtab = group(first + first[:1] * spare)
                     for k in range(len(first), len(first) + spare):
                         tab[k].max_new_tokens, tab[k].min_new_tokens = 1, 0
-                    codes, hidden = self.stream_open(e, npd, tr, pad, tab, max_row, eos, suppress_tokens, output_hidden_states, row_positions)
+                    codes, hidden = self.stream_open(e, npd, tr, pad, tab, max_row, eos, suppress_tokens, output_hidden_states, row_positions,
+                                                     warpers=wtab)
                     st["streams"] += 1
                     slot, seen, fresh = list(first) + [None] * spare, [0] * (len(first) + spare), set(first)
                     try:
@@ -884,14 +965,14 @@ class TalkerEngine:
                                 take = admissible(free, len(slot) - len(free)) if pooled else queue[:len(free)]
                                 at = 0
                                 for grp in admission_groups(take):
-                                    e, npd, tr, tab = group(grp)
-                                    self.stream_admit(free[at:at + len(grp)], e, npd, tr, tab)
+                                    e, npd, tr, tab, wtab = group(grp)
+                                    self.stream_admit(free[at:at + len(grp)], e, npd, tr, tab, warpers=wtab)
                                     at += len(grp)
                             else:
                                 take = [i for i in queue if lens[i] <= kv_len and kv_len + limit(i) <= self.max_seq][:len(free)]
                                 if take:
-                                    e, npd, tr, tab = group(take)
-                                    self.stream_admit(free[:len(take)], e, npd, tr, tab)
+                                    e, npd, tr, tab, wtab = group(take)
+                                    self.stream_admit(free[:len(take)], e, npd, tr, tab, warpers=wtab)
                             if take:
                                 for b, r in zip(free, take):
                                     slot[b], seen[b] = r, 0
@@ -926,6 +1007,7 @@ class TalkerEngine:
                          temperature=0.9, subtalker_dosample=True, subtalker_top_k=50, subtalker_top_p=1.0, subtalker_temperature=0.9,
                          eos_token_id: Optional[int] = None, repetition_penalty=1.05, suppress_tokens: Optional[List[int]] = None,
                          output_hidden_states: bool = True, seed=None, packet_frames: int = 4, row_positions: bool = False,
+                         min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None, no_repeat_ngram_size=None,
                          **unused) -> TalkerGenerateOutput:
         """`generate(..., schedule="refill")`: the packets of `_refill_stream` (its arguments and schedule) collected per request.
         Returns the requests in the order given, in `generate`'s structure: codes (N, F, G) with eos in codebook 0 behind a request's
@@ -940,7 +1022,8 @@ class TalkerEngine:
                                           subtalker_top_p=subtalker_top_p, subtalker_temperature=subtalker_temperature, eos_token_id=eos,
                                           repetition_penalty=repetition_penalty, suppress_tokens=suppress_tokens,
                                           output_hidden_states=output_hidden_states, seed=seed, packet_frames=packet_frames,
-                                          row_positions=row_positions):
+                                          row_positions=row_positions, min_p=min_p, typical_p=typical_p, epsilon_cutoff=epsilon_cutoff,
+                                          eta_cutoff=eta_cutoff, no_repeat_ngram_size=no_repeat_ngram_size):
             for e in packet.rows:
                 if e.restart:         # a preempted request starts again at frame 0: what it had delivered is replayed
                     parts[e.request], hparts[e.request] = [], []
@@ -959,6 +1042,14 @@ class TalkerEngine:
             if hidden_all is not None:
                 hidden_all[i, :n] = torch.cat(hparts[i])
         return TalkerGenerateOutput(codes=codes_all, hidden=hidden_all, tokens=tokens, n_frames=F)
+
+    @_lib.locked
+    def sampler_class(self):
+        """`qtts_talker_sampler_class`: (talker, code predictor) sampler kernels of the open stream or the last call -- 0 launch
+        constants (a scalar call), 1 `sample_kernel_v2`, 2 `sample_kernel`, 3 `sample_warp_kernel` (talker only)."""
+        a, b = C.c_int32(0), C.c_int32(0)
+        _lib.check(self._lib.qtts_talker_sampler_class(self._h, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
 
     @_lib.locked
     def debug_logits(self) -> torch.Tensor:
