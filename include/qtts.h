@@ -56,7 +56,9 @@ const char* qtts_last_error(void);
  * + qtts_talker_stream_begin_admitting_rows, qtts_talker_stream_row_lens, qtts_talker_stream_mode -- three entry points added, no
  * signature and no struct layout changed: qtts_talker_stats is byte for byte what it was, so a v15 binding keeps working and one that
  * needs the new calls finds out by looking the symbols up; still 15: + qtts_row_warpers, qtts_talker_set_row_warpers,
- * qtts_talker_sampler_class -- a new struct and two entry points, no existing signature or struct changed). */
+ * qtts_talker_sampler_class -- a new struct and two entry points, no existing signature or struct changed; still 15:
+ * + qtts_codec_stream_prime_rows, qtts_codec_stream_prime_tail -- two entry points added, no signature and no struct changed; a binding
+ * that needs them finds out by looking the symbols up). */
 #define QTTS_ABI_VERSION 15
 int qtts_abi_version(void);
 
@@ -168,6 +170,23 @@ int qtts_codec_stream_push(qtts_codec* c, const int64_t* codes_dev, int32_t n_fr
 int qtts_codec_stream_reset_rows(qtts_codec* c, int32_t n_rows, const int32_t* row_ids_host, void* stream);
 int qtts_codec_stream_push_rows(qtts_codec* c, int32_t n_rows, const int32_t* row_ids_host, const int64_t* codes_dev, int32_t n_frames,
                                 float* wav_dev, void* stream);
+/* Priming: sequences START in the listed slots with frames in front of them that are decoded but never heard -- a voice-clone reference,
+ * which the reference implementation decodes as cat([ref_code, codes]) and cuts off the waveform (qwen3_tts_model.py:612-631).
+ *   prime_rows: slot row_ids_host[m] is left exactly where qtts_codec_stream_reset_rows followed by a qtts_codec_stream_push_rows of its
+ *     own n_frames_host[m] frames would leave it (every conv carry, the roped q|k|v rows of every transformer layer, the position
+ *     = n_frames_host[m]); the reset is implied, no PCM is written and no final conv is launched.  codes_dev int64 (n_rows, num_quantizers,
+ *     n_max); row m's frames are the LAST n_frames_host[m] columns of its block (right-aligned), each in [1, n_max]; the leading columns
+ *     are never read.  Slots not listed are untouched.  All rows are primed by one set of launches whatever their lengths (the padding is
+ *     masked in the attention, skipped by the RoPE positions and written as zeros in front of every stateful layer), and only the last
+ *     qtts_codec_stream_prime_tail frames go through the upsampling stack: behind the transformer every layer has a finite reach, so
+ *     the carries depend on no earlier frame.  Switch QTTS_CODEC_PRIME_TAIL=0 (qtts_set_option): all n_max frames go through (A/B).
+ *   prime_tail: that number of frames, derived from the upsampling rates (10 for the released rates (2, 2) and (8, 5, 4, 3)).
+ * Refusals as for the per-slot calls above, before anything is launched (a refused call changes no slot); QTTS_ERR_ARG also for an
+ * n_frames_host[m] outside [1, n_max] (the message names the row); QTTS_ERR_LIMIT by the workspace rule, with n_max frames per row in
+ * the transformer and the tail behind it. */
+int qtts_codec_stream_prime_rows(qtts_codec* c, int32_t n_rows, const int32_t* row_ids_host, const int64_t* codes_dev,
+                                 const int32_t* n_frames_host, int32_t n_max, void* stream);
+int qtts_codec_stream_prime_tail(qtts_codec* c, int32_t* tail_frames_host);
 
 /* Test/diagnostic hook: run Qwen3TTSTokenizerV2Decoder.forward on codes_dev (B, Q, T) up to and including
  * `stage` and copy that stage's activation, channel-last float (B, L, C), to out_dev (capacity `cap` floats).

@@ -105,7 +105,8 @@ ABI_VERSION = 15          # include/qtts.h; bumped on any signature change
 # every symbol include/qtts.h declares (checked by tests/test_host_logic.py::test_abi_exports_every_declared_symbol without a GPU)
 SYMBOLS = ["qtts_last_error", "qtts_abi_version", "qtts_set_option", "qtts_get_option", "qtts_codec_create", "qtts_codec_destroy", "qtts_codec_bind",
            "qtts_codec_finalize", "qtts_codec_forward", "qtts_codec_decode", "qtts_codec_forward_stage",
-           "qtts_codec_stream_begin", "qtts_codec_stream_push", "qtts_codec_stream_reset_rows", "qtts_codec_stream_push_rows", "qtts_codec_get_stats",
+           "qtts_codec_stream_begin", "qtts_codec_stream_push", "qtts_codec_stream_reset_rows", "qtts_codec_stream_push_rows", "qtts_codec_stream_prime_rows",
+           "qtts_codec_stream_prime_tail", "qtts_codec_get_stats",
            "qtts_encoder_create", "qtts_encoder_destroy", "qtts_encoder_bind", "qtts_encoder_finalize", "qtts_encoder_frames",
            "qtts_encoder_encode",
            "qtts_speaker_create", "qtts_speaker_destroy", "qtts_speaker_bind", "qtts_speaker_finalize", "qtts_speaker_mel_frames",
@@ -180,6 +181,8 @@ def load_library():
     lib.qtts_codec_stream_push.argtypes = [vp, vp, i32, f32p, vp]
     lib.qtts_codec_stream_reset_rows.argtypes = [vp, i32, C.POINTER(C.c_int32), vp]
     lib.qtts_codec_stream_push_rows.argtypes = [vp, i32, C.POINTER(C.c_int32), vp, i32, f32p, vp]
+    lib.qtts_codec_stream_prime_rows.argtypes = [vp, i32, C.POINTER(C.c_int32), vp, C.POINTER(C.c_int32), i32, vp]
+    lib.qtts_codec_stream_prime_tail.argtypes = [vp, C.POINTER(C.c_int32)]
     lib.qtts_encoder_create.argtypes = [C.POINTER(EncoderConfigC), C.POINTER(vp)]
     lib.qtts_encoder_destroy.argtypes = [vp]
     lib.qtts_encoder_destroy.restype = None

@@ -206,6 +206,39 @@ class CodecDecoderEngine:
                                                              C.c_void_p(wav.data_ptr()), self._stream()))
         return wav.unsqueeze(1)
 
+    @property
+    def prime_tail_frames(self) -> int:
+        """Frames of a reference that `stream_prime_rows` sends through the upsampling stack (include/qtts.h
+        `qtts_codec_stream_prime_tail`): behind the transformer the decoder's state depends on no earlier frame."""
+        n = C.c_int32()
+        _lib.check(self._lib.qtts_codec_stream_prime_tail(self._h, C.byref(n)))
+        return int(n.value)
+
+    @_lib.locked
+    def stream_prime_rows(self, row_ids: List[int], codes: torch.Tensor, n_frames: List[int]):
+        """A sequence starts in each listed slot behind `n_frames[m]` frames that are decoded but not heard -- a voice-clone reference
+        (include/qtts.h `qtts_codec_stream_prime_rows`): codes (len(row_ids), Q, n_max) int64, row m's frames RIGHT-ALIGNED in its block
+        (the last n_frames[m] columns; the columns before them are ignored).  Each slot is left where `stream_reset_rows` and a
+        `stream_push_rows` of its own frames would leave it, so that the packets pushed next equal `forward(cat(ref, codes))` behind the
+        reference's samples; rows of different lengths share one set of launches, and no PCM is made."""
+        self._check_codes(codes, 1)
+        M, _, n_max = codes.shape
+        if M != len(row_ids) or M != len(n_frames):
+            raise ValueError(f"stream_prime_rows: {len(row_ids)} row ids and {len(n_frames)} lengths for {M} rows of codes")
+        if M < 1 or n_max < 1:
+            raise ValueError(f"stream_prime_rows: nothing to prime ({M} rows, {n_max} frames)")
+        codes = codes.to(self.device, torch.long).contiguous()
+        nf = [int(n) for n in n_frames]
+        if all(1 <= n <= n_max for n in nf):            # (a bad length is the library's to refuse: its message names the row)
+            real = torch.arange(n_max, device=codes.device)[None, :] >= torch.tensor([n_max - n for n in nf], device=codes.device)[:, None]
+            seen = codes[real[:, None, :].expand_as(codes)]
+            if int(seen.min()) < 0 or int(seen.max()) >= self.config.codebook_size:
+                raise ValueError("stream_prime_rows: code index out of range")
+        ids = (C.c_int32 * M)(*[int(r) for r in row_ids])
+        lens = (C.c_int32 * M)(*nf)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.qtts_codec_stream_prime_rows(self._h, M, ids, C.c_void_p(codes.data_ptr()), lens, int(n_max), self._stream()))
+
     def stream(self, left_context_size: int = 25) -> "CodecStreamDecoder":
         """A packet-by-packet decoder bound to this engine (see CodecStreamDecoder)."""
         return CodecStreamDecoder(self.forward, self.config.total_upsample, left_context_size)

@@ -177,6 +177,7 @@ struct qtts_codec {
     int stream_B = 0;                   // 0 = no session
     std::vector<int64_t> slot_t;        // [B] frames decoded so far, per slot
     DevBuf stream_meta;                 // the rows of one push: [M] slot map | [M] first position | [M] left-pad count of the KV window
+                                        // (a prime adds: | [M] leading pad frames of the block | [M] leading pad frames of the tail)
     // Pageable host memory, rewritten by the next call: right only because the runtime has consumed a pageable source (staged it, or
     // waited for the copy) when hipMemcpyAsync returns -- so a push or reset may block the host on the stream for that copy.  A
     // hipGraph of the push needs pinned memory here.  (stream_reset_host alike.)
@@ -187,7 +188,12 @@ struct qtts_codec {
     void stream_check_rows(int n_rows, const int* ids, const char* who) const;
     void stream_reset_rows(int n_rows, const int* ids, hipStream_t st);
     void stream_push_rows(int n_rows, const int* ids, const int64_t* codes, int n, float* wav, hipStream_t st);
-    void stream_run(int M, const int64_t* codes, int n, float* wav, hipStream_t st, bool dry);
+    // a prime's share of stream_run: sequence m is right-aligned in a block of n frames behind lead[m] pad frames; only the last `tail`
+    // frames go through the upsampling stack, where sequence m has tail_lead[m] pad frames (device arrays in stream_meta)
+    struct PrimePlan { const int* lead; const int* tail_lead; int tail; };
+    int prime_tail = 0;                 // frames of a reference that the carries behind the transformer depend on (finalize)
+    void stream_prime_rows(int n_rows, const int* ids, const int64_t* codes, const int* n_frames, int n_max, hipStream_t st);
+    void stream_run(int M, const int64_t* codes, int n, float* wav, hipStream_t st, bool dry, const PrimePlan* prime = nullptr);
     void stream_push(const int64_t* codes, int n, float* wav, hipStream_t st);
 
     std::vector<float>& P(const std::string& n) {
@@ -516,6 +522,22 @@ void qtts_codec::finalize() {
     if (bf16) for (auto& b : buf16) b.alloc(buf_elems * sizeof(bf16_t));
     err_flag.alloc(4);
     QTTS_CHECK_HIP(hipMemset(err_flag.p, 0, 4));
+    {   // stream_prime_rows: the smallest number of trailing frames for which the last h input rows of every stateful layer behind the
+        // transformer are exact when the frames before them are replaced by zeros -- the stack walked backwards, `need` = trailing rows
+        // of the layer's input that must be exact (every layer here is causal with a finite reach)
+        int need = 6;                                                        // final conv k=7: its carry
+        const int dil3[3] = {1, 3, 9};
+        for (int i = c.n_upsample_rates - 1; i >= 0; --i) {
+            for (int j = 2; j >= 0; --j) need += 6 * dil3[j];                // residual unit: conv k=7, dilation dil (its carry: 6 * dil <= need)
+            need = (need + c.upsample_rates[i] - 1) / c.upsample_rates[i] + 1;   // k = 2r transposed conv: output block t reads rows t, t-1
+        }
+        need += 6;                                                           // decoder.0 k=7
+        for (int u = c.n_upsampling_ratios - 1; u >= 0; --u) {
+            need += 6;                                                       // ConvNeXt dwconv k=7
+            need = (need + c.upsampling_ratios[u] - 1) / c.upsampling_ratios[u];    // k = s = f transposed conv: column-local
+        }
+        prime_tail = need;
+    }
     host.clear();  // host copies no longer needed
     finalized = true;
 }
@@ -755,8 +777,8 @@ void qtts_codec::stream_begin(int B) {
     // stream, which does not order against the null stream when it is a non-blocking one (PyTorch's pool streams are).
     QTTS_CHECK_HIP(hipDeviceSynchronize());
     QTTS_REQUIRE((int)carry.size() <= StreamCarryTable::MAX, QTTS_ERR_LIMIT, "codec stream: more stateful layers than the reset table holds");
-    stream_meta.ensure((size_t)3 * B * sizeof(int));
-    stream_meta_host.assign((size_t)3 * B, 0);
+    stream_meta.ensure((size_t)5 * B * sizeof(int));
+    stream_meta_host.assign((size_t)5 * B, 0);
     stream_reset_ids.ensure((size_t)B * sizeof(int));
     stream_reset_host.assign(B, 0);
     stream_B = B;
@@ -817,8 +839,40 @@ void qtts_codec::stream_push_rows(int M, const int* ids, const int64_t* codes, i
     for (int m = 0; m < M; ++m) slot_t[ids[m]] += n;
 }
 
+// Sequences START in the M listed slots, sequence m with the last n_frames[m] columns of its (Q, n_max) block as the frames that came
+// before its first push (a voice-clone reference, decoded in front of the generated frames and cut off the waveform).  Afterwards every
+// carry and the position of slot ids[m] are what stream_reset_rows + a stream_push_rows of those frames alone leave -- from ONE set of
+// launches for all rows whatever their lengths, and with only the last prime_tail frames sent through the upsampling stack
+// (QTTS_CODEC_PRIME_TAIL=0: all of them, A/B).  The carries are overwritten whole, so no reset launch is needed.
+void qtts_codec::stream_prime_rows(int M, const int* ids, const int64_t* codes, const int* n_frames, int n_max, hipStream_t st) {
+    stream_check_rows(M, ids, "stream_prime_rows");
+    QTTS_REQUIRE(codes && n_frames && n_max >= 1, QTTS_ERR_ARG, "stream_prime_rows: null argument or n_max < 1");
+    for (int m = 0; m < M; ++m)
+        QTTS_REQUIRE(n_frames[m] >= 1 && n_frames[m] <= n_max, QTTS_ERR_ARG,
+                     "stream_prime_rows: row " + std::to_string(ids[m]) + ": n_frames " + std::to_string(n_frames[m]) + " is not in [1, n_max = " +
+                         std::to_string(n_max) + "]");
+    const int W1 = cfg.sliding_window - 1;
+    const int tail = QTTS_OPT_ON("QTTS_CODEC_PRIME_TAIL") ? std::min(prime_tail, n_max) : n_max;
+    int* meta = stream_meta_host.data();
+    const PrimePlan plan{stream_meta.as<int>() + 3 * M, stream_meta.as<int>() + 4 * M, tail};
+    stream_run(M, codes, n_max, nullptr, st, true, &plan);      // the workspace rule, before a carry is touched
+    for (int m = 0; m < M; ++m) {
+        const int lead = n_max - n_frames[m];
+        meta[m] = ids[m];
+        meta[M + m] = -lead;                                    // RoPE: the first real frame is frame 0
+        meta[2 * M + m] = W1 + lead;                            // attention: the (empty) carried window and the padding are masked
+        meta[3 * M + m] = lead;
+        meta[4 * M + m] = std::max(0, tail - n_frames[m]);
+    }
+    QTTS_CHECK_HIP(hipMemcpyAsync(stream_meta.p, meta, (size_t)5 * M * sizeof(int), hipMemcpyHostToDevice, st));
+    stream_run(M, codes, n_max, nullptr, st, false, &plan);
+    for (int m = 0; m < M; ++m) slot_t[ids[m]] = n_frames[m];
+}
+
 // The one orchestration of a push.  dry: walk the shapes and apply the workspace rule only, launch nothing.
-void qtts_codec::stream_run(int B, const int64_t* codes, int n, float* wav, hipStream_t st, bool dry) {
+// prime: the listed slots START sequences of their own lengths, right-aligned in the n frames (stream_prime_rows) -- the staging steps
+// write the padding and the carries in one launch, nothing behind the transformer sees more than the tail, no PCM is made.
+void qtts_codec::stream_run(int B, const int64_t* codes, int n, float* wav, hipStream_t st, bool dry, const PrimePlan* prime) {
     const auto& c = cfg;
     const int* slot = stream_meta.as<int>();
     const int* pos0 = slot + B;
@@ -843,12 +897,15 @@ void qtts_codec::stream_run(int B, const int64_t* codes, int n, float* wav, hipS
     size_t ci = 0;                                   // next carry
     // x: current activation, T rows per sequence of which the first `skip` are to be ignored, C channels
     float* x = nullptr; int T = n, skip = 0, C = 0;
+    const int* lead = prime ? prime->lead : nullptr; // prime: pad frames in front of each sequence, `rate` rows of x per frame
+    int rate = 1;
     auto stage = [&](float* dst) {                   // dst = [carry | valid rows of x]; refresh the carry; x <- dst
         Carry& k = carry[ci++];
         QTTS_REQUIRE(k.C == C, QTTS_ERR_STATE, "codec stream: carry/channel mismatch");
         const int nv = T - skip;
         fits((int64_t)B * (k.h + nv), C);
-        if (!dry) {
+        if (!dry && prime) launch_stage_prime_slots(x, T, skip, nv, lead, rate, k.d.as<float>(), slot, k.h, dst, B, C, st);
+        else if (!dry) {
             launch_stage_rows_slots(x, T, skip, nv, k.d.as<float>(), slot, k.h, dst, B, C, st);
             launch_save_tail_slots(dst, k.h + nv, k.d.as<float>(), slot, k.h, B, C, st);
         }
@@ -864,8 +921,9 @@ void qtts_codec::stream_run(int B, const int64_t* codes, int n, float* wav, hipS
     float* g = pool[1];
     x = pool[0]; C = c.codebook_dim;
     fits((int64_t)B * n, std::max(2 * vq, C));
-    if (!dry) launch_rvq_gather(codes, B, c.num_quantizers, n, (int64_t)c.num_quantizers * n, n, 1, 0, n, tables.as<float>(),
-                                c.codebook_size, vq, g, err_flag.as<int>(), st);
+    if (!dry && prime) launch_rvq_gather_lead(codes, B, c.num_quantizers, n, lead, tables.as<float>(), c.codebook_size, vq, g, err_flag.as<int>(), st);
+    else if (!dry) launch_rvq_gather(codes, B, c.num_quantizers, n, (int64_t)c.num_quantizers * n, n, 1, 0, n, tables.as<float>(),
+                                     c.codebook_size, vq, g, err_flag.as<int>(), st);
     G(rvq_out, g, 2 * vq, B * n, n, x, C);
     // ---- pre_conv k=3
     {
@@ -893,9 +951,12 @@ void qtts_codec::stream_run(int B, const int64_t* codes, int n, float* wav, hipS
             launch_rmsnorm(h, H, Ly.n1.as<float>(), c.rms_norm_eps, a, H, M, H, st);
             G(Ly.qkv, a, H, M, n, b2, qw);
             launch_rope_offset_rows(b2, qw, M, n, pos0, c.num_attention_heads + c.num_key_value_heads, c.head_dim, inv_freq.as<float>(), st);
-            // a <- [carried roped q|k|v rows | new rows]
-            launch_stage_rows_slots(b2, n, 0, n, k.d.as<float>(), slot, W1, a, B, qw, st);
-            launch_save_tail_slots(a, W1 + n, k.d.as<float>(), slot, W1, B, qw, st);
+            // a <- [carried roped q|k|v rows | new rows]  (prime: positions from -lead, W1 + lead masked rows, written as zeros)
+            if (prime) launch_stage_prime_slots(b2, n, 0, n, lead, 1, k.d.as<float>(), slot, W1, a, B, qw, st);
+            else {
+                launch_stage_rows_slots(b2, n, 0, n, k.d.as<float>(), slot, W1, a, B, qw, st);
+                launch_save_tail_slots(a, W1 + n, k.d.as<float>(), slot, W1, B, qw, st);
+            }
             AttnRowsParams ap{};
             ap.qkv = a; ap.ld = qw; ap.q_off = 0; ap.k_off = qd; ap.v_off = qd + kvd;
             ap.B = B; ap.T = W1 + n; ap.nh = c.num_attention_heads; ap.nkv = c.num_key_value_heads; ap.hd = c.head_dim;
@@ -911,13 +972,21 @@ void qtts_codec::stream_run(int B, const int64_t* codes, int n, float* wav, hipS
         G(out_proj, a, H, M, n, b2, c.latent_dim);
         x = b2; T = n; skip = 0; C = c.latent_dim;
     }
+    if (prime) {                                     // everything from here on has a finite reach: the last `tail` frames carry it
+        if (prime->tail < n) {
+            float* t = other({x});
+            if (!dry) launch_stage_rows(x, n, n - prime->tail, prime->tail, nullptr, 0, t, B, C, st);
+            x = t; T = prime->tail;
+        }
+        lead = prime->tail_lead;
+    }
     // ---- upsample: ConvTranspose(k = s = f, column-local) + ConvNeXt (dwconv k=7 carries 6 rows)
     for (int u = 0; u < c.n_upsampling_ratios; ++u) {
         const int f = c.upsampling_ratios[u];
         float* y = other({x});
         fits((int64_t)B * T * f, 4 * C);
         G(ups[u].tconv, x, C, B * T, T, y, f * C);
-        x = y; T *= f; skip *= f;
+        x = y; T *= f; skip *= f; rate *= f;
         float* s = other({x}); stage(s);                                   // x = staged y (also the residual)
         float* d = other({x});
         float* e = other({x, d});
@@ -945,7 +1014,7 @@ void qtts_codec::stream_run(int B, const int64_t* codes, int n, float* wav, hipS
             float* b = other({x, a});
             fits((int64_t)B * T * bk.r, bk.cout);
             G(bk.tconv, a, C, B * T, T, b, bk.r * bk.cout);
-            x = b; T *= bk.r; skip *= bk.r; C = bk.cout;
+            x = b; T *= bk.r; skip *= bk.r; rate *= bk.r; C = bk.cout;
         }
         for (int j = 0; j < 3; ++j) {
             auto& un = bk.u[j];
@@ -963,7 +1032,7 @@ void qtts_codec::stream_run(int B, const int64_t* codes, int n, float* wav, hipS
         float* s = other({x}); stage(s);
         float* a = other({x});
         QTTS_REQUIRE(C == final_c, QTTS_ERR_ARG, "final conv channel mismatch");
-        if (!dry) {
+        if (!dry && !prime) {                        // (a prime ends with the final conv's carry: no PCM)
             launch_snake(x, final_act.ea.as<float>(), final_act.ib.as<float>(), a, (int64_t)B * T, C, st);
             launch_final_conv(a, final_w.as<float>(), final_b, wav, nullptr, (int64_t)B * T, T, C, (int64_t)n * up_total, skip, st);
         }
@@ -1209,6 +1278,21 @@ int qtts_codec_stream_push_rows(qtts_codec* c, int32_t n_rows, const int32_t* ro
     QTTS_REQUIRE(c, QTTS_ERR_ARG, "null handle");
     c->stream_push_rows(n_rows, row_ids_host, codes_dev, n_frames, wav_dev, (hipStream_t)stream);
     c->check_codes_flag((hipStream_t)stream);
+    QTTS_API_END
+}
+int qtts_codec_stream_prime_rows(qtts_codec* c, int32_t n_rows, const int32_t* row_ids_host, const int64_t* codes_dev,
+                                 const int32_t* n_frames_host, int32_t n_max, void* stream) {
+    QTTS_API_BEGIN
+    QTTS_REQUIRE(c, QTTS_ERR_ARG, "null handle");
+    c->stream_prime_rows(n_rows, row_ids_host, codes_dev, n_frames_host, n_max, (hipStream_t)stream);
+    c->check_codes_flag((hipStream_t)stream);
+    QTTS_API_END
+}
+int qtts_codec_stream_prime_tail(qtts_codec* c, int32_t* tail_frames_host) {
+    QTTS_API_BEGIN
+    QTTS_REQUIRE(c && tail_frames_host, QTTS_ERR_ARG, "null argument");
+    QTTS_REQUIRE(c->finalized, QTTS_ERR_STATE, "codec: finalize() first");
+    *tail_frames_host = c->prime_tail;
     QTTS_API_END
 }
 

@@ -140,6 +140,14 @@ void launch_stage_rows_slots(const float* src, int src_T, int skip, int n, const
                              int M, int C, hipStream_t st);
 // state[slot[m]] = the last h rows of buf[m] (Tp rows per sequence)
 void launch_save_tail_slots(const float* buf, int Tp, float* state, const int* slot, int h, int M, int C, hipStream_t st);
+// Priming a slot (a sequence STARTS in it, left-padded inside its block): dst[m] = [h zero rows | lead[m] * rate zero rows | the rest of
+// src[m][skip : skip + n]], and state[slot[m]] = the last h rows of dst[m], in one launch.  The zeros are the causal left padding of a
+// sequence whose first row is row lead[m] * rate of the block; the carry is written, never read (lead: device array, one per sequence).
+void launch_stage_prime_slots(const float* src, int src_T, int skip, int n, const int* lead, int rate, float* state, const int* slot,
+                              int h, float* dst, int M, int C, hipStream_t st);
+// launch_rvq_gather on codes (M, Q, T) whose first lead[m] columns of sequence m are padding: never read, their rows written as zeros
+void launch_rvq_gather_lead(const int64_t* codes, int M, int Q, int T, const int* lead, const float* tables, int bins, int vq, float* out,
+                            int* err, hipStream_t st);
 // launch_rope_inplace with positions pos0[row / T] + (row % T), pos0 a device array with one entry per sequence
 void launch_rope_offset_rows(float* qkv, int ld, int rows, int T, const int* pos0, int n_heads_total, int hd, const float* inv_freq,
                              hipStream_t st);

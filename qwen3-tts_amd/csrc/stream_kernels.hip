@@ -59,6 +59,67 @@ void launch_save_tail_slots(const float* buf, int Tp, float* state, const int* s
     QTTS_CHECK_HIP(hipGetLastError());
 }
 
+// ---------------------------------------------------------------------------------- priming a slot
+// stream_prime_rows starts sequences of DIFFERENT lengths in one set of launches: sequence m is right-aligned in its block, so its first
+// lead[m] frames (lead[m] * rate rows at a stage that runs at `rate` rows per frame) are padding.  Every stateful layer must see them as
+// the causal zero padding of a sequence that starts behind them, and the stateless layers in between write bias terms into them; the
+// staging step is where every stateful layer's input passes, so it writes the zeros: dst[m] = [h zeros (the carry of a sequence that
+// starts) | lead zeros | src rows].  The carry -- the last h rows of dst[m] -- is stored by the block that wrote the row: stage_rows_slots
+// + save_tail_slots in one launch, and nothing reads the carry, so no block depends on another.
+__global__ __launch_bounds__(256) void stage_prime_slots_kernel(const float* src, int src_T, int skip, int n, const int* lead, int rate,
+                                                                float* state, const int* slot, int h, float* dst, int C4) {
+    const int r = blockIdx.x, m = blockIdx.y;
+    const bool pad = r < h + lead[m] * rate;
+    const float4* from = reinterpret_cast<const float4*>(src) + ((size_t)m * src_T + skip + (pad ? 0 : r - h)) * C4;
+    float4* to = reinterpret_cast<float4*>(dst) + ((size_t)m * (h + n) + r) * C4;
+    float4* keep = r >= n ? reinterpret_cast<float4*>(state) + ((size_t)slot[m] * h + (r - n)) * C4 : nullptr;
+    for (int c = threadIdx.x; c < C4; c += 256) {
+        const float4 v = pad ? make_float4(0.f, 0.f, 0.f, 0.f) : from[c];
+        to[c] = v;
+        if (keep) keep[c] = v;
+    }
+}
+void launch_stage_prime_slots(const float* src, int src_T, int skip, int n, const int* lead, int rate, float* state, const int* slot,
+                              int h, float* dst, int M, int C, hipStream_t st) {
+    QTTS_REQUIRE(C % 4 == 0 && n >= 1 && h >= 1 && skip >= 0 && skip + n <= src_T && M >= 1 && rate >= 1, QTTS_ERR_ARG,
+                 "stage_prime_slots: bad shape");
+    QTTS_REQUIRE(src && dst && state && slot && lead, QTTS_ERR_ARG, "stage_prime_slots: null argument");
+    hipLaunchKernelGGL(stage_prime_slots_kernel, dim3(h + n, M), dim3(256), 0, st, src, src_T, skip, n, lead, rate, state, slot, h, dst, C / 4);
+    QTTS_CHECK_HIP(hipGetLastError());
+}
+
+// rvq_gather (elementwise.hip) for the right-aligned blocks of a prime: codes (M, Q, T) contiguous, the first lead[m] columns of
+// sequence m are padding whose VALUES are not the caller's to define -- they are not read (no error flag, no table row), and their
+// output rows are zeros.  The real columns are summed in rvq_gather's order.
+__global__ __launch_bounds__(256) void rvq_gather_lead_kernel(const int64_t* codes, int Q, int T, const int* lead, const float* tables,
+                                                              int bins, int vq, float* out, int* err) {
+    const int row = blockIdx.x;          // m * T + t
+    const int m = row / T, t = row % T;
+    const bool pad = t < lead[m];
+    const int64_t* cp = codes + ((size_t)m * Q) * T + t;
+    if (!pad && threadIdx.x < Q && cp[(size_t)threadIdx.x * T] >= bins) *err = 1;
+    for (int j = threadIdx.x; j < 2 * vq; j += 256) {
+        float acc = 0.f;
+        if (!pad && j < vq) {
+            int64_t c = cp[0]; if (c < 0 || c >= bins) c = 0;
+            acc = tables[((size_t)c) * vq + j];
+        } else if (!pad) {
+            for (int q = 1; q < Q; ++q) {
+                int64_t c = cp[(size_t)q * T]; if (c < 0 || c >= bins) c = 0;
+                const float e = tables[((size_t)q * bins + c) * vq + (j - vq)];
+                acc = (q == 1) ? e : acc + e;
+            }
+        }
+        out[(size_t)row * 2 * vq + j] = acc;
+    }
+}
+void launch_rvq_gather_lead(const int64_t* codes, int M, int Q, int T, const int* lead, const float* tables, int bins, int vq, float* out,
+                            int* err, hipStream_t st) {
+    QTTS_REQUIRE(Q >= 1 && Q <= 256 && M >= 1 && T >= 1 && codes && lead && err, QTTS_ERR_ARG, "rvq_gather_lead: bad shape");
+    hipLaunchKernelGGL(rvq_gather_lead_kernel, dim3(M * T), dim3(256), 0, st, codes, Q, T, lead, tables, bins, vq, out, err);
+    QTTS_CHECK_HIP(hipGetLastError());
+}
+
 // rotate-half RoPE at positions pos0[row / T] + (row % T): T new frames per sequence, sequence m of the push starts at frame pos0[m]
 // of its own stream
 __global__ __launch_bounds__(256) void rope_offset_rows_kernel(float* qkv, int ld, int T, const int* pos0, int nheads, int hd,

@@ -657,12 +657,11 @@ class Qwen3TTSModel:
         return dict(ref_code=[it.ref_code for it in items], ref_spk_embedding=[it.ref_spk_embedding for it in items],
                     x_vector_only_mode=[it.x_vector_only_mode for it in items], icl_mode=[it.icl_mode for it in items])
 
-    @torch.no_grad()
-    def generate_voice_clone(self, text, language=None, ref_audio=None, ref_text=None, x_vector_only_mode=False,
-                             voice_clone_prompt=None, non_streaming_mode: bool = False, **kwargs
-                             ) -> Tuple[List[np.ndarray], int]:
+    def _voice_clone_inputs(self, who, text, language, ref_audio, ref_text, x_vector_only_mode, voice_clone_prompt):
+        """Argument handling of `generate_voice_clone` (qwen3_tts_model.py:460-590), shared with its streaming form: (texts, languages,
+        voice_clone_prompt dict, input_ids, ref_ids)."""
         if self.model.tts_model_type != "base":
-            raise self._unsupported("generate_voice_clone")
+            raise self._unsupported(who)
         texts = self._ensure_list(text)
         languages = self._lang_list(language, len(texts))
         if len(texts) != len(languages):
@@ -688,6 +687,14 @@ class Qwen3TTSModel:
         if ref_texts is not None:
             ref_ids = [None if rt is None or rt == "" else self._tokenize_texts([self._build_ref_text(rt)])[0]
                        for rt in ref_texts]
+        return texts, languages, vcp, input_ids, ref_ids
+
+    @torch.no_grad()
+    def generate_voice_clone(self, text, language=None, ref_audio=None, ref_text=None, x_vector_only_mode=False,
+                             voice_clone_prompt=None, non_streaming_mode: bool = False, **kwargs
+                             ) -> Tuple[List[np.ndarray], int]:
+        texts, languages, vcp, input_ids, ref_ids = self._voice_clone_inputs("generate_voice_clone", text, language, ref_audio, ref_text,
+                                                                             x_vector_only_mode, voice_clone_prompt)
         gen_kwargs = self._merge_generate_kwargs(**kwargs)
         codes_list, _ = self.model.generate(input_ids=input_ids, ref_ids=ref_ids, voice_clone_prompt=vcp,
                                             languages=languages, non_streaming_mode=non_streaming_mode, **gen_kwargs)
@@ -709,11 +716,10 @@ class Qwen3TTSModel:
         return out, fs
 
     # ---- voice design (qwen3_tts_model.py:637-730)
-    @torch.no_grad()
-    def generate_voice_design(self, text, instruct, language=None, non_streaming_mode: bool = True, **kwargs
-                              ) -> Tuple[List[np.ndarray], int]:
+    def _voice_design_inputs(self, who, text, instruct, language):
+        """Argument handling of `generate_voice_design` (qwen3_tts_model.py:637-700), shared with its streaming form."""
         if self.model.tts_model_type != "voice_design":
-            raise self._unsupported("generate_voice_design")
+            raise self._unsupported(who)
         texts = self._ensure_list(text)
         languages = self._lang_list(language, len(texts))
         instructs = self._ensure_list(instruct)
@@ -723,6 +729,12 @@ class Qwen3TTSModel:
             raise ValueError(f"Batch size mismatch: text={len(texts)}, language={len(languages)}, instruct={len(instructs)}")
         self._validate_languages(languages)
         input_ids = self._tokenize_texts([self._build_assistant_text(t) for t in texts])
+        return texts, languages, instructs, input_ids
+
+    @torch.no_grad()
+    def generate_voice_design(self, text, instruct, language=None, non_streaming_mode: bool = True, **kwargs
+                              ) -> Tuple[List[np.ndarray], int]:
+        texts, languages, instructs, input_ids = self._voice_design_inputs("generate_voice_design", text, instruct, language)
         gen_kwargs = self._merge_generate_kwargs(**kwargs)
         codes_list, _ = self.model.generate(input_ids=input_ids, instruct_ids=self._instruct_ids(instructs),
                                             languages=languages, non_streaming_mode=non_streaming_mode, **gen_kwargs)
@@ -774,44 +786,10 @@ class Qwen3TTSModel:
         dec = self.model.speech_tokenizer.model.decoder
         cb = dec.config.codebook_size
         if schedule in ("refill", "continuous"):
-            rows = self.model.talker.max_batch
-            if dec.max_batch < rows:
-                raise ValueError(f"stream_custom_voice(schedule={schedule!r}): the codec decoder's max_batch ({dec.max_batch}) is smaller than "
-                                 f"the talker's ({rows}); every talker row needs a slot of the codec stream")
-            sr = int(self.model.speech_tokenizer.model.output_sample_rate)
-            dec.stream_begin(rows)
-            made, delivered = [0] * len(texts), [0] * len(texts)      # samples decoded since the request (re)started / handed out
-            for record in self.model.generate_stream(input_ids=input_ids, instruct_ids=self._instruct_ids(instructs), languages=languages,
-                                                     speakers=speakers, non_streaming_mode=non_streaming_mode,
-                                                     packet_frames=packet_frames, **gen_kwargs):
-                started = [e.row for e in record.rows if e.first]
-                if started:
-                    dec.stream_reset_rows(started)
-                for e in record.rows:
-                    if e.first:
-                        made[e.request] = 0
-                live = [e for e in record.rows if e.codes.shape[0] > 0]
-                if not live:
-                    continue
-                k = max(int(e.codes.shape[0]) for e in live)
-                # a row that gained fewer frames than the packet has finished: it is padded with code 0, its extra samples are dropped,
-                # and its slot is reset before the next request uses it
-                if any(int(e.codes.shape[0]) < k and not e.last for e in live):
-                    raise RuntimeError("stream_custom_voice: a running row fell behind its packet")
-                batch = torch.zeros(len(live), k, live[0].codes.shape[-1], dtype=torch.long, device=self.device)
-                for m, e in enumerate(live):
-                    batch[m, : e.codes.shape[0]] = e.codes.clamp(min=0, max=cb - 1)
-                wav = dec.stream_push_rows([e.row for e in live], batch.transpose(1, 2))[:, 0]
-                up = wav.shape[-1] // k
-                out = [np.zeros(0, np.float32) for _ in texts]
-                for m, e in enumerate(live):
-                    seg = wav[m, : int(e.codes.shape[0]) * up]
-                    r, at = e.request, made[e.request]
-                    made[r] = at + int(seg.shape[0])
-                    if made[r] > delivered[r]:           # (a replay after a restart: only what lies beyond the delivered samples)
-                        out[r] = seg[max(0, delivered[r] - at):].cpu().numpy().astype(np.float32)
-                        delivered[r] = made[r]
-                yield out, sr
+            self._begin_slot_stream("stream_custom_voice", schedule)
+            yield from self._stream_slot_packets("stream_custom_voice", len(texts), self.model.generate_stream(
+                input_ids=input_ids, instruct_ids=self._instruct_ids(instructs), languages=languages, speakers=speakers,
+                non_streaming_mode=non_streaming_mode, packet_frames=packet_frames, **gen_kwargs))
             return
         stream = dec.stream(left_context_size)
         for parts in self.model.generate_stream(input_ids=input_ids, instruct_ids=self._instruct_ids(instructs), languages=languages,
@@ -828,6 +806,143 @@ class Qwen3TTSModel:
             up = wav.shape[-1] // k
             yield [wav[i, : int(p.shape[0]) * up].cpu().numpy().astype(np.float32) for i, p in enumerate(parts)], \
                 int(self.model.speech_tokenizer.model.output_sample_rate)
+
+    # ---- the packet loop over the codec's slot decoder, shared by the streaming wrappers
+    def _begin_slot_stream(self, who: str, schedule):
+        """Every talker row owns a slot of the codec's state-carrying decoder: open the session."""
+        dec = self.model.speech_tokenizer.model.decoder
+        rows = self.model.talker.max_batch
+        if dec.max_batch < rows:
+            raise ValueError(f"{who}(schedule={schedule!r}): the codec decoder's max_batch ({dec.max_batch}) is smaller than "
+                             f"the talker's ({rows}); every talker row needs a slot of the codec stream")
+        dec.stream_begin(rows)
+
+    def _stream_slot_packets(self, who: str, n_req: int, records, ref_codes=None):
+        """`records`: `RefillPacket`s of the talker (`generate_stream(schedule="refill" | "continuous")`, or `_wave_records`).  Yields
+        (list of np.float32 arrays, one per request, sample_rate) per packet that carried frames.  A request that starts in a row --
+        also again, after a preemption -- gets the row's codec slot as a new sequence: primed with its reference codes where
+        `ref_codes[request]` holds some (all such rows of a packet in ONE `stream_prime_rows` call), reset otherwise.  Only PCM beyond
+        what the request has already delivered is handed out."""
+        dec = self.model.speech_tokenizer.model.decoder
+        cb = dec.config.codebook_size
+        sr = int(self.model.speech_tokenizer.model.output_sample_rate)
+        made, delivered = [0] * n_req, [0] * n_req                # samples decoded since the request (re)started / handed out
+        for record in records:
+            started = [e for e in record.rows if e.first]
+            primed = [e for e in started if ref_codes is not None and ref_codes[e.request] is not None]
+            plain = [e.row for e in started if ref_codes is None or ref_codes[e.request] is None]
+            if plain:
+                dec.stream_reset_rows(plain)
+            if primed:                                            # (T, Q) each, right-aligned in one (M, Q, n_max) block
+                refs = [ref_codes[e.request].to(self.device, torch.long) for e in primed]
+                n_max = max(int(r.shape[0]) for r in refs)
+                block = torch.zeros(len(refs), refs[0].shape[-1], n_max, dtype=torch.long, device=self.device)
+                for m, r in enumerate(refs):
+                    block[m, :, n_max - r.shape[0]:] = r.transpose(0, 1)
+                dec.stream_prime_rows([e.row for e in primed], block, [int(r.shape[0]) for r in refs])
+            for e in started:
+                made[e.request] = 0
+            live = [e for e in record.rows if e.codes.shape[0] > 0]
+            if not live:
+                continue
+            k = max(int(e.codes.shape[0]) for e in live)
+            # a row that gained fewer frames than the packet has finished: it is padded with code 0, its extra samples are dropped,
+            # and its slot is reset before the next request uses it
+            if any(int(e.codes.shape[0]) < k and not e.last for e in live):
+                raise RuntimeError(f"{who}: a running row fell behind its packet")
+            batch = torch.zeros(len(live), k, live[0].codes.shape[-1], dtype=torch.long, device=self.device)
+            for m, e in enumerate(live):
+                batch[m, : e.codes.shape[0]] = e.codes.clamp(min=0, max=cb - 1)
+            wav = dec.stream_push_rows([e.row for e in live], batch.transpose(1, 2))[:, 0]
+            up = wav.shape[-1] // k
+            out = [np.zeros(0, np.float32) for _ in range(n_req)]
+            for m, e in enumerate(live):
+                seg = wav[m, : int(e.codes.shape[0]) * up]
+                r, at = e.request, made[e.request]
+                made[r] = at + int(seg.shape[0])
+                if made[r] > delivered[r]:               # (a replay after a restart: only what lies beyond the delivered samples)
+                    out[r] = seg[max(0, delivered[r] - at):].cpu().numpy().astype(np.float32)
+                    delivered[r] = made[r]
+            yield out, sr
+
+    def _wave_records(self, n_req: int, gen_kwargs: Dict[str, Any], stream_wave):
+        """The default schedule as `RefillPacket`s: the requests run as waves of the talker's `max_batch` rows, one wave after the other,
+        as `Qwen3TTSForConditionalGeneration.generate` runs them (per-request sequences sliced per wave; one seed s: wave w samples with
+        s + w, or request i with s + i once any knob is per request).  `stream_wave(slice, **kwargs)` is `generate_stream` on one wave;
+        request i of a wave occupies row i."""
+        from .talker import RefillPacket, RefillRow, _is_row_seq, _warp_table
+        mb = self.model.talker.max_batch
+        seed = gen_kwargs.get("seed")
+        knobs = {k: v for k, v in gen_kwargs.items() if k != "seed"}
+        warped = {k: knobs[k] for k in _WARP_ARGS if knobs.get(k) is not None}
+        per_request = any(_is_row_seq(v) for v in knobs.values()) or _is_row_seq(seed) or _warp_table(n_req, **warped) is not None
+        if per_request and not _is_row_seq(seed):
+            seed = [int(seed) + i for i in range(n_req)] if seed is not None else None
+        for b0 in range(0, n_req, mb):
+            sl = slice(b0, b0 + mb)
+            wave = {k: (list(v[sl]) if _is_row_seq(v) else v) for k, v in knobs.items()}
+            wave["seed"] = list(seed[sl]) if _is_row_seq(seed) else (None if seed is None else int(seed) + b0 // mb)
+            for n, parts in enumerate(stream_wave(sl, **wave)):
+                k = max(int(p.shape[0]) for p in parts)
+                yield RefillPacket([RefillRow(request=b0 + i, row=i, codes=p, first=n == 0, last=int(p.shape[0]) < k)
+                                    for i, p in enumerate(parts) if n == 0 or p.shape[0] > 0])
+
+    @torch.no_grad()
+    def stream_voice_clone(self, text, language=None, ref_audio=None, ref_text=None, x_vector_only_mode=False, voice_clone_prompt=None,
+                           non_streaming_mode: bool = False, packet_frames: int = 4, schedule: Optional[str] = None, **kwargs):
+        """`generate_voice_clone` as a generator of PCM packets: the same arguments, validation and errors; yields (list of np.float32
+        arrays, one per request, sample_rate) every `packet_frames` frames, as `stream_custom_voice` does.  A request's array is empty
+        while it is queued, in a packet in which it gained no frame, and once it has finished.
+
+        The reference decodes `cat([ref_code, codes])` and cuts the reference's share off the waveform (qwen3_tts_model.py:612-631).
+        Here every talker row owns a slot of the codec's state-carrying decoder, under every schedule (there is no `left_context_size`
+        and no chunked rule): when a request starts in a row its slot is primed with the request's `ref_code`
+        (`CodecDecoderEngine.stream_prime_rows`: the state "the reference has just been decoded", without its PCM), all rows that
+        start in one packet in one call; an x-vector-only request has no reference codes and its slot is only reset.  A request's
+        concatenated audio equals `generate_voice_clone`'s for the same seeds while reference + generated frames fit one chunk of
+        the one-shot decode (300 frames); beyond that the one-shot audio follows the chunked rule and this one stays the
+        whole-sequence decode.
+
+        `schedule=None`: waves of the talker's `max_batch` requests, one wave after the other; "refill" / "continuous": as
+        `stream_custom_voice`.  On a model with a KV page pool a preempted request's slot is primed again before its frames are
+        replayed, and only PCM beyond what was delivered is yielded."""
+        texts, languages, vcp, input_ids, ref_ids = self._voice_clone_inputs("stream_voice_clone", text, language, ref_audio, ref_text,
+                                                                             x_vector_only_mode, voice_clone_prompt)
+        gen_kwargs = self._merge_generate_kwargs(**kwargs)
+        ref_codes = vcp.get("ref_code", None)
+        self._begin_slot_stream("stream_voice_clone", schedule)
+        if schedule is not None:
+            records = self.model.generate_stream(input_ids=input_ids, ref_ids=ref_ids, voice_clone_prompt=vcp, languages=languages,
+                                                 non_streaming_mode=non_streaming_mode, packet_frames=packet_frames, schedule=schedule,
+                                                 **gen_kwargs)
+        else:
+            def stream_wave(sl, **wave):
+                return self.model.generate_stream(
+                    input_ids=input_ids[sl], ref_ids=None if ref_ids is None else ref_ids[sl],
+                    voice_clone_prompt={k: (v[sl] if isinstance(v, list) else v) for k, v in vcp.items()}, languages=languages[sl],
+                    non_streaming_mode=non_streaming_mode, packet_frames=packet_frames, **wave)
+            records = self._wave_records(len(texts), gen_kwargs, stream_wave)
+        yield from self._stream_slot_packets("stream_voice_clone", len(texts), records, ref_codes)
+
+    @torch.no_grad()
+    def stream_voice_design(self, text, instruct, language=None, non_streaming_mode: bool = True, packet_frames: int = 4,
+                            schedule: Optional[str] = None, **kwargs):
+        """`generate_voice_design` as a generator of PCM packets, on the packet loop of `stream_voice_clone` (no reference codes, so
+        every slot is only reset): the same arguments, validation and errors."""
+        texts, languages, instructs, input_ids = self._voice_design_inputs("stream_voice_design", text, instruct, language)
+        gen_kwargs = self._merge_generate_kwargs(**kwargs)
+        instruct_ids = self._instruct_ids(instructs)
+        self._begin_slot_stream("stream_voice_design", schedule)
+        if schedule is not None:
+            records = self.model.generate_stream(input_ids=input_ids, instruct_ids=instruct_ids, languages=languages,
+                                                 non_streaming_mode=non_streaming_mode, packet_frames=packet_frames, schedule=schedule,
+                                                 **gen_kwargs)
+        else:
+            def stream_wave(sl, **wave):
+                return self.model.generate_stream(input_ids=input_ids[sl], instruct_ids=instruct_ids[sl], languages=languages[sl],
+                                                  non_streaming_mode=non_streaming_mode, packet_frames=packet_frames, **wave)
+            records = self._wave_records(len(texts), gen_kwargs, stream_wave)
+        yield from self._stream_slot_packets("stream_voice_design", len(texts), records)
 
     # ---- custom voice (qwen3_tts_model.py:732-840)
     @torch.no_grad()
