@@ -14,6 +14,7 @@ import torch
 
 from . import _lib
 from .config import TalkerConfig
+from .refill import RefillPacket, RefillPolicy, RefillRow, widest_opener
 
 
 def _default_inv_freq(theta: float, head_dim: int) -> torch.Tensor:
@@ -27,7 +28,6 @@ def _fresh_seed() -> int:
     return int(torch.randint(0, 2 ** 62, (), dtype=torch.int64).item())
 
 
-
 @dataclass
 class TalkerGenerateOutput:
     codes: torch.Tensor        # (B, n_frames, G) int64, untrimmed (M:2280)
@@ -39,27 +39,28 @@ class TalkerGenerateOutput:
 
 
 @dataclass
-class RefillRow:
-    """One row's share of a `RefillPacket`."""
-    request: int               # index of the request in the list given to `generate_stream`
-    row: int                   # the row (= codec slot) the request occupies
-    codes: torch.Tensor        # (k, G) int64: the frames the request gained in this packet (a copy; k may be 0 when `last`)
-    first: bool                # the request started with this packet: whatever the row held before belongs to another request
-    last: bool                 # the request finished: its frames end here (first eos in codebook 0, or its own limit)
-    hidden: Optional[torch.Tensor] = None        # (k, H) float32 `past_hidden` of these frames, when asked for
-    restart: bool = False      # (pooled engines) the request was preempted and starts again at frame 0 with this packet: set together with
-                               # `first`; drop what was collected for it -- the replayed frames equal the dropped ones
-
-
-@dataclass
-class RefillPacket:
-    """What `generate_stream(..., schedule="refill")` yields after every packet of the running stream: one entry per row whose occupant
-    gained frames or finished in it."""
-    rows: List[RefillRow]
+class _Call:
+    """A generation call as `TalkerEngine._prepare` hands it to `generate`, `generate_stream` and the refill schedules: checked, on the
+    device, settings resolved.  Exactly one of `rows` (the per-row table; `warp` may come with it) and `sp` (the scalar path) is set."""
+    B: int
+    T: int
+    n_pad: List[int]
+    lens: List[int]            # T - n_pad
+    emb: torch.Tensor          # (B, T, H) fp32 on the device, contiguous (as `trail` (B, Tt, H) and `pad` (H,))
+    trail: torch.Tensor
+    pad: torch.Tensor
+    eos: int
+    suppress: List[int]
+    npad_c: Any                # n_pad and suppress as the C ABI takes them
+    sup_c: Any
+    rows: Any                  # `_lib.RowSamplingC` x B, or None
+    warp: Any                  # `_lib.RowWarpersC` x B, or None
+    sp: Any                    # `_lib.SamplingC`, or None
+    max_new_tokens: int        # clamped to the KV capacity; on the table the largest limit (buffers are sized by it)
+    min_new_tokens: Any        # as given (the scalar path passes it on; the table holds its own)
 
 
 _SKIP_PREFIXES = ("speaker_encoder.",)
-
 
 
 def _as_index(v):
@@ -105,6 +106,20 @@ def _resolve_top(top_k, top_p):
 
 _ROW_ARGS = ("do_sample", "top_k", "top_p", "temperature", "repetition_penalty", "subtalker_dosample", "subtalker_top_k",
              "subtalker_top_p", "subtalker_temperature", "max_new_tokens", "min_new_tokens", "seed")
+
+
+def _fill_sampling(e, r):
+    """The sampling knobs and the seed of a call (`_lib.SamplingC`) or of one request (`_lib.RowSamplingC`), which name them alike, from
+    the values `r` (a dict over `_ROW_ARGS`), checked as HF checks them.  No seed draws a fresh one."""
+    _check_warpers(**{k: r[k] for k in ("top_k", "top_p", "temperature", "subtalker_top_k", "subtalker_top_p", "subtalker_temperature")})
+    e.do_sample = 1 if r["do_sample"] else 0
+    e.top_k, e.top_p = _resolve_top(r["top_k"], r["top_p"])
+    e.temperature = float(r["temperature"]) if r["temperature"] is not None else 1.0
+    e.repetition_penalty = float(r["repetition_penalty"]) if r["repetition_penalty"] is not None else 1.0
+    e.subtalker_dosample = 1 if r["subtalker_dosample"] else 0
+    e.subtalker_top_k, e.subtalker_top_p = _resolve_top(r["subtalker_top_k"], r["subtalker_top_p"])
+    e.subtalker_temperature = float(r["subtalker_temperature"]) if r["subtalker_temperature"] is not None else 1.0
+    e.seed = int(r["seed"]) & 0xFFFFFFFFFFFFFFFF if r["seed"] is not None else _fresh_seed()
 
 
 # the talker's remaining HF sampling controls (include/qtts.h `qtts_row_warpers`): per request like the knobs above, always on the table
@@ -299,13 +314,15 @@ class TalkerEngine:
             max_new_tokens = room
         return max_new_tokens
 
-    def _row_table(self, B: int, T: int, force: bool = False, **kw):
+    def _row_table(self, B: int, T, force: bool = False, **kw):
         """The per-request settings table of a call (include/qtts.h `qtts_row_sampling`), or None when every argument of `_ROW_ARGS`
         is a scalar (the scalar path).  Any of them may be a sequence of length B; scalars are broadcast.  Every element goes through
         the checks a scalar goes through (`_check_warpers`, `_resolve_top`, `_clamp_new_tokens`).  Seeds: a `None` (the whole argument
         or one element) draws a fresh seed for each such row; ONE integer s gives request b the seed s + b, so that requests never share
-        their draws unless a seed list says so.  `force`: the call has a warper table (`_warp_table`), which lives on the per-row table:
-        scalars are broadcast.  Returns (ctypes array of B entries, the largest max_new_tokens)."""
+        their draws unless a seed list says so.  `T`: the prompt length the limits are clamped against, one for the batch or a list of
+        B (the refill schedules: every request against its own prompt).  `force`: the table is built whatever the arguments are (a call
+        with a warper table, `_warp_table`, which lives on the per-row table; the refill schedules): scalars are broadcast.  Returns
+        (ctypes array of B entries, the largest max_new_tokens)."""
         if not force and not any(_is_row_seq(kw[k]) for k in _ROW_ARGS):
             return None
         cols = {}
@@ -324,21 +341,12 @@ class TalkerEngine:
         rows = (_lib.RowSamplingC * B)()
         for b in range(B):
             r = {k: cols[k][b] for k in _ROW_ARGS}
-            _check_warpers(**{k: r[k] for k in ("top_k", "top_p", "temperature", "subtalker_top_k", "subtalker_top_p",
-                                                "subtalker_temperature")})
             e = rows[b]
-            e.do_sample = 1 if r["do_sample"] else 0
-            e.top_k, e.top_p = _resolve_top(r["top_k"], r["top_p"])
-            e.temperature = float(r["temperature"]) if r["temperature"] is not None else 1.0
-            e.repetition_penalty = float(r["repetition_penalty"]) if r["repetition_penalty"] is not None else 1.0
-            e.subtalker_dosample = 1 if r["subtalker_dosample"] else 0
-            e.subtalker_top_k, e.subtalker_top_p = _resolve_top(r["subtalker_top_k"], r["subtalker_top_p"])
-            e.subtalker_temperature = float(r["subtalker_temperature"]) if r["subtalker_temperature"] is not None else 1.0
+            _fill_sampling(e, r)
             if r["max_new_tokens"] is None or int(r["max_new_tokens"]) < 1:
                 raise ValueError(f"`max_new_tokens` of request {b} must be a positive integer, but is {r['max_new_tokens']}")
-            e.max_new_tokens = self._clamp_new_tokens(T, int(r["max_new_tokens"]))
+            e.max_new_tokens = self._clamp_new_tokens(T[b] if isinstance(T, list) else T, int(r["max_new_tokens"]))
             e.min_new_tokens = int(r["min_new_tokens"]) if r["min_new_tokens"] is not None else 0
-            e.seed = int(r["seed"]) & 0xFFFFFFFFFFFFFFFF if r["seed"] is not None else _fresh_seed()
         return rows, max(int(rows[b].max_new_tokens) for b in range(B))
 
     # ------------------------------------------------------------------ generate (seam S2)
@@ -383,7 +391,7 @@ class TalkerEngine:
 
     @_lib.locked
     def generate(self, *args, **kw) -> TalkerGenerateOutput:
-        """Seam S2 (`talker.generate`, M:2272): see `_generate_once` for the arguments.  One thing is added around it: a generation
+        """Seam S2 (`talker.generate`, M:2272): see `_prepare` and `_generate_once` for the arguments.  One thing is added around it: a generation
         that ended on the fused launches' give-up flag (a consumer workgroup lost its producers -- another PROCESS on the device took
         the compute units; csrc/talker_engine.hip: check_fused_flag) has produced nothing the caller saw, and the engine has left the
         fused launches for good, so the request is re-run ONCE here on the separate launches instead of surfacing a bare error.
@@ -405,20 +413,18 @@ class TalkerEngine:
                           "this engine now runs the separate launches and the request is re-run once")
             return self._generate_once(*args, **kw)
 
-    def _generate_once(self, inputs_embeds: torch.Tensor, attention_mask: torch.Tensor, trailing_text_hidden: torch.Tensor,
+    def _prepare(self, queue_mode: bool, inputs_embeds: torch.Tensor, attention_mask: torch.Tensor, trailing_text_hidden: torch.Tensor,
                  tts_pad_embed: torch.Tensor, max_new_tokens: int = 2048, min_new_tokens: int = 2,
                  do_sample: bool = True, top_k: Optional[int] = 50, top_p: Optional[float] = 1.0,
                  temperature: Optional[float] = 0.9, subtalker_dosample: bool = True,
                  subtalker_top_k: Optional[int] = 50, subtalker_top_p: Optional[float] = 1.0,
                  subtalker_temperature: Optional[float] = 0.9, eos_token_id: Optional[int] = None,
-                 repetition_penalty: float = 1.05, suppress_tokens: Optional[List[int]] = None,
-                 output_hidden_states: bool = True, return_dict_in_generate: bool = True,
-                 seed: Optional[int] = None, teacher_codes: Optional[torch.Tensor] = None,
-                 logit_steps: Optional[List[int]] = None, min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None,
-                 no_repeat_ngram_size=None, **unused) -> TalkerGenerateOutput:
-        """`teacher_codes` (B, F, G) switches on the diagnostic teacher-forced mode (include/qtts.h `qtts_talker_set_teacher`):
-        greedy, exactly F frames; the engine's own choices come back in `.own`, the raw cb-0 logits of the token steps listed in
-        `logit_steps` in `.logits_trace`.
+                 repetition_penalty: float = 1.05, suppress_tokens: Optional[List[int]] = None, seed: Optional[int] = None,
+                 min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None, no_repeat_ngram_size=None, **unused) -> _Call:
+        """The arguments of a generation call (`generate`, `generate_stream` and the refill schedules take them alike), checked and
+        made ready: shapes, the left-padded mask, the per-row and warper tables or the scalar settings, eos and the suppress list, the
+        three tensors on the device.  `queue_mode` (the refill schedules): the rows are a queue of requests, not a batch -- any number
+        of them, always on the per-row table, every request's limit clamped against the room its OWN prompt leaves.
 
         Per-request settings: each of `do_sample`, `top_k`, `top_p`, `temperature`, `repetition_penalty`, the four `subtalker_*`
         knobs, `max_new_tokens`, `min_new_tokens` and `seed` is one value for the batch (as in the reference) or a sequence of B
@@ -432,19 +438,14 @@ class TalkerEngine:
         Any of them that is on puts the call on the per-row table (scalars are broadcast; ONE integer seed s gives request b the seed
         s + b) and the talker's sampler becomes `sample_warp_kernel` (`sampler_class()` reports 3).  Any OTHER keyword this signature
         does not name is still swallowed."""
-        c = self.config
+        c, dev = self.config, self.device
         if inputs_embeds.dim() != 3 or inputs_embeds.shape[-1] != c.hidden_size:
             raise ValueError(f"inputs_embeds must be (B, T, {c.hidden_size})")
         B, T, H = inputs_embeds.shape
-        if B > self.max_batch:
-            raise ValueError(f"batch {B} exceeds max_batch {self.max_batch} given at construction")
-        self._live_batch = int(B)
-        if teacher_codes is not None:
-            if teacher_codes.dim() != 3 or teacher_codes.shape[0] != B or teacher_codes.shape[2] != c.num_code_groups:
-                raise ValueError(f"teacher_codes must be (B, F, {c.num_code_groups})")
-            F_t = int(teacher_codes.shape[1])
-            max_new_tokens = min_new_tokens = F_t + 1
-            do_sample = subtalker_dosample = False
+        if not queue_mode:
+            if B > self.max_batch:
+                raise ValueError(f"batch {B} exceeds max_batch {self.max_batch} given at construction")
+            self._live_batch = int(B)
         mask = attention_mask.to("cpu", torch.long)
         if mask.shape != (B, T):
             raise ValueError("attention_mask must be (B, T)")
@@ -453,35 +454,23 @@ class TalkerEngine:
         expect = (torch.arange(T)[None, :] >= n_pad[:, None]).long()
         if not torch.equal(mask, expect) or int(n_pad.max()) >= T:
             raise ValueError("attention_mask must be left-padded: [0]*n_pad + [1]*(T-n_pad) per row")
+        n_pad = [int(x) for x in n_pad]
+        lens = [T - x for x in n_pad]
+        # (a request keeps its entries of both tables through queueing, admission and restart)
         warp = _warp_table(B, min_p=min_p, typical_p=typical_p, epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff,
                            no_repeat_ngram_size=no_repeat_ngram_size)
-        table = self._row_table(B, T, force=warp is not None, do_sample=do_sample, top_k=top_k, top_p=top_p, temperature=temperature,
-                                repetition_penalty=repetition_penalty, subtalker_dosample=subtalker_dosample,
-                                subtalker_top_k=subtalker_top_k, subtalker_top_p=subtalker_top_p,
-                                subtalker_temperature=subtalker_temperature, max_new_tokens=max_new_tokens,
-                                min_new_tokens=min_new_tokens, seed=seed)
-        eos = c.codec_eos_token_id if eos_token_id is None else int(eos_token_id)
-        if suppress_tokens is None:
-            suppress_tokens = []
+        knobs = dict(do_sample=do_sample, top_k=top_k, top_p=top_p, temperature=temperature, repetition_penalty=repetition_penalty,
+                     subtalker_dosample=subtalker_dosample, subtalker_top_k=subtalker_top_k, subtalker_top_p=subtalker_top_p,
+                     subtalker_temperature=subtalker_temperature, max_new_tokens=max_new_tokens, min_new_tokens=min_new_tokens, seed=seed)
+        table = self._row_table(B, lens if queue_mode else T, force=queue_mode or warp is not None, **knobs)
+        rows = sp = None
         if table is not None:
-            if teacher_codes is not None:
-                raise ValueError("teacher_codes takes scalar settings, not per-request sequences")
             rows, max_new_tokens = table                  # buffers are sized by the largest limit
         else:
             max_new_tokens = self._clamp_new_tokens(T, int(max_new_tokens))
-            _check_warpers(top_k=top_k, top_p=top_p, temperature=temperature, subtalker_top_k=subtalker_top_k,
-                           subtalker_top_p=subtalker_top_p, subtalker_temperature=subtalker_temperature)
             sp = _lib.SamplingC()
-            sp.do_sample = 1 if do_sample else 0
-            sp.top_k, sp.top_p = _resolve_top(top_k, top_p)
-            sp.temperature = float(temperature) if temperature is not None else 1.0
-            sp.repetition_penalty = float(repetition_penalty) if repetition_penalty is not None else 1.0
-            sp.subtalker_dosample = 1 if subtalker_dosample else 0
-            sp.subtalker_top_k, sp.subtalker_top_p = _resolve_top(subtalker_top_k, subtalker_top_p)
-            sp.subtalker_temperature = float(subtalker_temperature) if subtalker_temperature is not None else 1.0
-            sp.seed = int(seed) & 0xFFFFFFFFFFFFFFFF if seed is not None else _fresh_seed()
-
-        dev = self.device
+            _fill_sampling(sp, knobs)
+        suppress = [] if suppress_tokens is None else list(suppress_tokens)
         emb = inputs_embeds.to(dev, torch.float32).contiguous()
         trail = trailing_text_hidden.to(dev, torch.float32).contiguous()
         if trail.dim() != 3 or trail.shape[0] != B or trail.shape[2] != H or trail.shape[1] < 1:
@@ -489,12 +478,31 @@ class TalkerEngine:
         pad = tts_pad_embed.to(dev, torch.float32).reshape(-1).contiguous()
         if pad.numel() != H:
             raise ValueError("tts_pad_embed must have H elements")
+        return _Call(B=B, T=T, n_pad=n_pad, lens=lens, emb=emb, trail=trail, pad=pad,
+                     eos=c.codec_eos_token_id if eos_token_id is None else int(eos_token_id), suppress=suppress,
+                     npad_c=(C.c_int32 * B)(*n_pad), sup_c=(C.c_int32 * max(1, len(suppress)))(*[int(x) for x in suppress]),
+                     rows=rows, warp=warp, sp=sp, max_new_tokens=max_new_tokens, min_new_tokens=min_new_tokens)
+
+    def _generate_once(self, inputs_embeds: torch.Tensor, *args, output_hidden_states: bool = True,
+                       teacher_codes: Optional[torch.Tensor] = None, logit_steps: Optional[List[int]] = None, **kw) -> TalkerGenerateOutput:
+        """One static batch (`generate`, the "waves" schedule); the arguments are `_prepare`'s.  `teacher_codes` (B, F, G) switches on
+        the diagnostic teacher-forced mode (include/qtts.h `qtts_talker_set_teacher`): greedy, exactly F frames; the engine's own
+        choices come back in `.own`, the raw cb-0 logits of the token steps listed in `logit_steps` in `.logits_trace`."""
+        c, dev = self.config, self.device
+        if teacher_codes is not None:
+            if teacher_codes.dim() != 3 or teacher_codes.shape[0] != inputs_embeds.shape[0] or teacher_codes.shape[2] != c.num_code_groups:
+                raise ValueError(f"teacher_codes must be (B, F, {c.num_code_groups})")
+            F_t = int(teacher_codes.shape[1])
+            kw.update(max_new_tokens=F_t + 1, min_new_tokens=F_t + 1, do_sample=False, subtalker_dosample=False)
+        p = self._prepare(False, inputs_embeds, *args, **kw)
+        if teacher_codes is not None and p.rows is not None:
+            raise ValueError("teacher_codes takes scalar settings, not per-request sequences")
+        B, T, H, max_new_tokens = p.B, p.T, c.hidden_size, p.max_new_tokens
+        emb, trail, pad, suppress_tokens = p.emb, p.trail, p.pad, p.suppress
         max_frames = max(1, max_new_tokens - 1)
         codes = torch.zeros(B, max_frames, c.num_code_groups, dtype=torch.int64, device=dev)
         hidden = torch.zeros(B, max_frames, H, dtype=torch.float32, device=dev) if output_hidden_states else None
         tokens = torch.full((B, max_new_tokens), -1, dtype=torch.int64, device=dev)
-        npad_c = (C.c_int32 * B)(*[int(x) for x in n_pad])
-        sup_c = (C.c_int32 * max(1, len(suppress_tokens)))(*[int(x) for x in suppress_tokens])
         n_frames = C.c_int32(0)
         own = trace = None
         if teacher_codes is not None:
@@ -517,7 +525,7 @@ class TalkerEngine:
         cur = torch.cuda.current_stream(dev)
         self._stream.wait_stream(cur)
         with torch.cuda.device(dev), torch.cuda.stream(self._stream):
-            _lib.check(self._lib.qtts_talker_prefill(self._h, C.c_void_p(emb.data_ptr()), B, T, npad_c,
+            _lib.check(self._lib.qtts_talker_prefill(self._h, C.c_void_p(emb.data_ptr()), B, T, p.npad_c,
                                                      C.c_void_p(trail.data_ptr()), trail.shape[1],
                                                      C.c_void_p(pad.data_ptr()), self._s()))
             if teacher_codes is not None:
@@ -527,13 +535,13 @@ class TalkerEngine:
             out_c = (C.c_void_p(codes.data_ptr()), C.c_void_p(hidden.data_ptr()) if hidden is not None else None,
                      C.c_void_p(tokens.data_ptr()), C.byref(n_frames), self._s())
             try:
-                if table is not None:
-                    if warp is not None:
-                        _lib.check(self._lib.qtts_talker_set_row_warpers(self._h, warp, B))
-                    _lib.check(self._lib.qtts_talker_generate_rows(self._h, rows, B, eos, sup_c, len(suppress_tokens), *out_c))
+                if p.rows is not None:
+                    if p.warp is not None:
+                        _lib.check(self._lib.qtts_talker_set_row_warpers(self._h, p.warp, B))
+                    _lib.check(self._lib.qtts_talker_generate_rows(self._h, p.rows, B, p.eos, p.sup_c, len(suppress_tokens), *out_c))
                 else:
-                    _lib.check(self._lib.qtts_talker_generate(self._h, C.byref(sp), int(max_new_tokens), int(min_new_tokens), eos,
-                                                              sup_c, len(suppress_tokens), *out_c))
+                    _lib.check(self._lib.qtts_talker_generate(self._h, C.byref(p.sp), int(max_new_tokens), int(p.min_new_tokens), p.eos,
+                                                              p.sup_c, len(suppress_tokens), *out_c))
             finally:
                 if teacher_codes is not None:
                     _lib.check(self._lib.qtts_talker_set_teacher(self._h, None, 0, None, None, None))
@@ -559,85 +567,37 @@ class TalkerEngine:
         admission rule, per-row table and seed rules: `_refill_stream`); yields one `RefillPacket` per packet of the running stream
         instead of a block of codes.  Concatenating a request's packets gives exactly the codes `generate(schedule="refill")` returns
         for it.  `schedule="continuous"`: the same on ONE stream with per-row positions (`_refill_stream(row_positions=True)`)."""
+        kw = dict(max_new_tokens=max_new_tokens, min_new_tokens=min_new_tokens, do_sample=do_sample, top_k=top_k, top_p=top_p,
+                  temperature=temperature, subtalker_dosample=subtalker_dosample, subtalker_top_k=subtalker_top_k,
+                  subtalker_top_p=subtalker_top_p, subtalker_temperature=subtalker_temperature, eos_token_id=eos_token_id,
+                  repetition_penalty=repetition_penalty, suppress_tokens=suppress_tokens, seed=seed, min_p=min_p, typical_p=typical_p,
+                  epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff, no_repeat_ngram_size=no_repeat_ngram_size)
         if schedule in ("refill", "continuous"):
             yield from self._refill_stream(inputs_embeds, attention_mask, trailing_text_hidden, tts_pad_embed, packet_frames=packet_frames,
-                                           max_new_tokens=max_new_tokens, min_new_tokens=min_new_tokens, do_sample=do_sample, top_k=top_k,
-                                           top_p=top_p, temperature=temperature, subtalker_dosample=subtalker_dosample,
-                                           subtalker_top_k=subtalker_top_k, subtalker_top_p=subtalker_top_p,
-                                           subtalker_temperature=subtalker_temperature, eos_token_id=eos_token_id,
-                                           repetition_penalty=repetition_penalty, suppress_tokens=suppress_tokens, seed=seed,
-                                           row_positions=schedule == "continuous", min_p=min_p, typical_p=typical_p,
-                                           epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff, no_repeat_ngram_size=no_repeat_ngram_size)
+                                           row_positions=schedule == "continuous", **kw)
             return
         if schedule != "waves":
             raise ValueError(f"`schedule` must be 'waves', 'refill' or 'continuous', but is {schedule!r}")
-        c = self.config
-        if inputs_embeds.dim() != 3 or inputs_embeds.shape[-1] != c.hidden_size:
-            raise ValueError(f"inputs_embeds must be (B, T, {c.hidden_size})")
-        B, T, H = inputs_embeds.shape
-        if B > self.max_batch:
-            raise ValueError(f"batch {B} exceeds max_batch {self.max_batch} given at construction")
-        self._live_batch = int(B)
         if packet_frames < 1:
             raise ValueError("packet_frames must be >= 1")
-        mask = attention_mask.to("cpu", torch.long)
-        if mask.shape != (B, T):
-            raise ValueError("attention_mask must be (B, T)")
-        n_pad = (1 - mask).sum(-1)
-        expect = (torch.arange(T)[None, :] >= n_pad[:, None]).long()
-        if not torch.equal(mask, expect) or int(n_pad.max()) >= T:
-            raise ValueError("attention_mask must be left-padded: [0]*n_pad + [1]*(T-n_pad) per row")
-        warp = _warp_table(B, min_p=min_p, typical_p=typical_p, epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff,
-                           no_repeat_ngram_size=no_repeat_ngram_size)
-        table = self._row_table(B, T, force=warp is not None, do_sample=do_sample, top_k=top_k, top_p=top_p, temperature=temperature,
-                                repetition_penalty=repetition_penalty, subtalker_dosample=subtalker_dosample,
-                                subtalker_top_k=subtalker_top_k, subtalker_top_p=subtalker_top_p,
-                                subtalker_temperature=subtalker_temperature, max_new_tokens=max_new_tokens,
-                                min_new_tokens=min_new_tokens, seed=seed)
-        eos = c.codec_eos_token_id if eos_token_id is None else int(eos_token_id)
-        suppress_tokens = list(suppress_tokens or [])
-        if table is not None:
-            rows, max_new_tokens = table
-        else:
-            max_new_tokens = self._clamp_new_tokens(T, int(max_new_tokens))
-            _check_warpers(top_k=top_k, top_p=top_p, temperature=temperature, subtalker_top_k=subtalker_top_k,
-                           subtalker_top_p=subtalker_top_p, subtalker_temperature=subtalker_temperature)
-            sp = _lib.SamplingC()
-            sp.do_sample = 1 if do_sample else 0
-            sp.top_k, sp.top_p = _resolve_top(top_k, top_p)
-            sp.temperature = float(temperature) if temperature is not None else 1.0
-            sp.repetition_penalty = float(repetition_penalty) if repetition_penalty is not None else 1.0
-            sp.subtalker_dosample = 1 if subtalker_dosample else 0
-            sp.subtalker_top_k, sp.subtalker_top_p = _resolve_top(subtalker_top_k, subtalker_top_p)
-            sp.subtalker_temperature = float(subtalker_temperature) if subtalker_temperature is not None else 1.0
-            sp.seed = int(seed) & 0xFFFFFFFFFFFFFFFF if seed is not None else _fresh_seed()
-        dev = self.device
-        emb = inputs_embeds.to(dev, torch.float32).contiguous()
-        trail = trailing_text_hidden.to(dev, torch.float32).contiguous()
-        if trail.dim() != 3 or trail.shape[0] != B or trail.shape[2] != H or trail.shape[1] < 1:
-            raise ValueError("trailing_text_hidden must be (B, Tt >= 1, H)")
-        pad = tts_pad_embed.to(dev, torch.float32).reshape(-1).contiguous()
-        if pad.numel() != H:
-            raise ValueError("tts_pad_embed must have H elements")
-        codes = torch.zeros(B, max(1, max_new_tokens - 1), c.num_code_groups, dtype=torch.int64, device=dev)
-        npad_c = (C.c_int32 * B)(*[int(x) for x in n_pad])
-        sup_c = (C.c_int32 * max(1, len(suppress_tokens)))(*[int(x) for x in suppress_tokens])
+        p = self._prepare(False, inputs_embeds, attention_mask, trailing_text_hidden, tts_pad_embed, **kw)
+        dev, B, n_sup = self.device, p.B, len(p.suppress)
+        codes = torch.zeros(B, max(1, p.max_new_tokens - 1), self.config.num_code_groups, dtype=torch.int64, device=dev)
         total, fin, nf = C.c_int32(0), C.c_int32(0), C.c_int32(0)
         with self._lock:
             self._stream.wait_stream(torch.cuda.current_stream(dev))
             with torch.cuda.device(dev), torch.cuda.stream(self._stream):
-                _lib.check(self._lib.qtts_talker_prefill(self._h, C.c_void_p(emb.data_ptr()), B, T, npad_c,
-                                                         C.c_void_p(trail.data_ptr()), trail.shape[1],
-                                                         C.c_void_p(pad.data_ptr()), self._s()))
-                if table is not None:
-                    if warp is not None:
-                        _lib.check(self._lib.qtts_talker_set_row_warpers(self._h, warp, B))
-                    _lib.check(self._lib.qtts_talker_stream_begin_rows(self._h, rows, B, eos, sup_c, len(suppress_tokens),
+                _lib.check(self._lib.qtts_talker_prefill(self._h, C.c_void_p(p.emb.data_ptr()), B, p.T, p.npad_c,
+                                                         C.c_void_p(p.trail.data_ptr()), p.trail.shape[1],
+                                                         C.c_void_p(p.pad.data_ptr()), self._s()))
+                if p.rows is not None:
+                    if p.warp is not None:
+                        _lib.check(self._lib.qtts_talker_set_row_warpers(self._h, p.warp, B))
+                    _lib.check(self._lib.qtts_talker_stream_begin_rows(self._h, p.rows, B, p.eos, p.sup_c, n_sup,
                                                                        C.c_void_p(codes.data_ptr()), None, self._s()))
                 else:
-                    _lib.check(self._lib.qtts_talker_stream_begin(self._h, C.byref(sp), int(max_new_tokens), int(min_new_tokens), eos,
-                                                                  sup_c, len(suppress_tokens), C.c_void_p(codes.data_ptr()), None,
-                                                                  self._s()))
+                    _lib.check(self._lib.qtts_talker_stream_begin(self._h, C.byref(p.sp), int(p.max_new_tokens), int(p.min_new_tokens),
+                                                                  p.eos, p.sup_c, n_sup, C.c_void_p(codes.data_ptr()), None, self._s()))
             seen = 0
             try:
                 while not fin.value:
@@ -770,12 +730,7 @@ class TalkerEngine:
         self._open = None
         return int(nf.value)
 
-    def _refill_stream(self, inputs_embeds: torch.Tensor, attention_mask: torch.Tensor, trailing_text_hidden: torch.Tensor,
-                       tts_pad_embed: torch.Tensor, max_new_tokens=2048, min_new_tokens=2, do_sample=True, top_k=50, top_p=1.0,
-                       temperature=0.9, subtalker_dosample=True, subtalker_top_k=50, subtalker_top_p=1.0, subtalker_temperature=0.9,
-                       eos_token_id: Optional[int] = None, repetition_penalty=1.05, suppress_tokens: Optional[List[int]] = None,
-                       output_hidden_states: bool = False, seed=None, packet_frames: int = 4, row_positions: bool = False,
-                       min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None, no_repeat_ngram_size=None, **unused):
+    def _refill_stream(self, *args, output_hidden_states: bool = False, packet_frames: int = 4, row_positions: bool = False, **kw):
         """The refill schedule, packet by packet (`generate_stream(..., schedule="refill")`; `generate(..., schedule="refill")` collects
         what this yields): any number of requests on `max_batch` rows.  The rows start with the requests of the longest prompts; the
         stream runs in packets of `packet_frames` frames; after each packet every row whose occupant gained frames or finished is
@@ -808,207 +763,56 @@ class TalkerEngine:
         for the whole call.  A pool that is tight against a long first prompt therefore serves the whole request list on that narrower
         stream, also after the long prompt has retired and its pages are free (`last_refill["occupancy"]` is measured against
         `max_batch` and shows it).  It costs throughput, never correctness; size the pool to at least
-        `max_batch x ceil(longest prompt / 16)` pages to open at full width."""
-        c, dev = self.config, self.device
-        if inputs_embeds.dim() != 3 or inputs_embeds.shape[-1] != c.hidden_size:
-            raise ValueError(f"inputs_embeds must be (B, T, {c.hidden_size})")
-        N, T, H = inputs_embeds.shape
+        `max_batch x ceil(longest prompt / 16)` pages to open at full width.
+
+        The arguments are `_prepare`'s (its queue mode).  Every decision above is `refill.RefillPolicy`'s; this generator drives the
+        engine with it and hands it what the engine reports."""
         if packet_frames < 1:
             raise ValueError("packet_frames must be >= 1")
-        mask = attention_mask.to("cpu", torch.long)
-        n_pad = (1 - mask).sum(-1)
-        if mask.shape != (N, T) or not torch.equal(mask, (torch.arange(T)[None, :] >= n_pad[:, None]).long()) or int(n_pad.max()) >= T:
-            raise ValueError("attention_mask must be (B, T), left-padded: [0]*n_pad + [1]*(T-n_pad) per row")
-        lens = [T - int(x) for x in n_pad]
-        if not _is_row_seq(seed):
-            seed = [int(seed) + i for i in range(N)] if seed is not None else [None] * N
-        rows, _ = self._row_table(N, 0, do_sample=do_sample, top_k=top_k, top_p=top_p, temperature=temperature,
-                                  repetition_penalty=repetition_penalty, subtalker_dosample=subtalker_dosample,
-                                  subtalker_top_k=subtalker_top_k, subtalker_top_p=subtalker_top_p,
-                                  subtalker_temperature=subtalker_temperature, max_new_tokens=max_new_tokens,
-                                  min_new_tokens=min_new_tokens, seed=seed)
-        # the requests' warpers (`_warp_table`; None: no request has any): a request keeps its entry through queueing, admission and restart
-        warps = _warp_table(N, min_p=min_p, typical_p=typical_p, epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff,
-                            no_repeat_ngram_size=no_repeat_ngram_size)
-        for i in range(N):           # a request's limit inside the capacity its own prompt leaves (`_clamp_new_tokens`)
-            rows[i].max_new_tokens = self._clamp_new_tokens(lens[i], int(rows[i].max_new_tokens))
-        eos = c.codec_eos_token_id if eos_token_id is None else int(eos_token_id)
-        suppress_tokens = list(suppress_tokens or [])
-        emb = inputs_embeds.to(dev, torch.float32)
-        trail = trailing_text_hidden.to(dev, torch.float32)
-        if trail.dim() != 3 or trail.shape[0] != N or trail.shape[2] != H or trail.shape[1] < 1:
-            raise ValueError("trailing_text_hidden must be (B, Tt >= 1, H)")
-        pad = tts_pad_embed.to(dev, torch.float32).reshape(-1)
-        if pad.numel() != H:
-            raise ValueError("tts_pad_embed must have H elements")
-        mb = self.max_batch
-        max_row = max(int(rows[i].max_new_tokens) for i in range(N))
-        queue = sorted(range(N), key=lambda i: (-lens[i], i))
-        st = dict(streams=0, admit_calls=0, admitted_rows=0, frames_run=0, row_frames=0, graph_captures=0, max_row_len=0,
-                  pool_pages=self.kv_pages or 0, peak_pages=0, preemptions=0)
-        limit = lambda i: int(rows[i].max_new_tokens)
-        pooled = bool(row_positions and self.kv_pages)
-        # (a pool that holds max_seq keys for every row can never run dry: nothing is preempted, so admission is not held back either)
-        tight = pooled and self.kv_pages < self.max_batch * (-(-self.max_seq // 16))
-        pages_of = lambda n_keys: -(-int(n_keys) // 16)
-        restarted = set()
+        p = self._prepare(True, *args, **kw)
+        pol = RefillPolicy(p.lens, [int(r.max_new_tokens) for r in p.rows], self.max_batch, self.max_seq, packet_frames, row_positions,
+                           self.kv_pages)
 
-        def step_need(slot, seen):
-            """the host's page count of the next packet: (pages the running rows still need, pages free once the finished rows have given
-            theirs back, pages in use during the packet) -- the engine's own rule (include/qtts.h, stream_step on a pooled engine)"""
-            held, free, _ = self.stream_kv()
-            row_len = self.stream_row_lens()
-            need, avail, used = 0, free, 0
-            for b, r in enumerate(slot):
-                if r is None:
-                    avail += held[b]
-                    continue
-                want = pages_of(row_len[b] + min(packet_frames, max(0, limit(r) - 1 - seen[b])))
-                need += max(0, want - held[b])
-                used += max(want, held[b])
-            return need, avail, used
-
-        def admissible(free_rows, running):
-            """pooled: the head of the queue that fits -- prompt pages of its admission groups + one page per row then running <= free"""
-            if not tight:
-                return queue[:len(free_rows)]
-            _, free, _ = self.stream_kv()
-            take = []
-            for i in queue[:len(free_rows)]:
-                cand = take + [i]
-                prompt_pages = sum(len(grp) * pages_of(max(lens[j] for j in grp)) for grp in admission_groups(cand))
-                if prompt_pages + (running + len(cand) if running or take else 0) > free:
-                    break
-                take = cand
-            return take
-
-        def admission_groups(idx):
-            """per-row positions: `idx` in queue order, cut into groups in each of which the padded length + every limit fits max_seq"""
-            groups = []
-            for i in idx:
-                cand = (groups[-1] if groups else []) + [i]
-                Tg = max(lens[j] for j in cand)
-                if groups and all(Tg + limit(j) <= self.max_seq for j in cand):
-                    groups[-1] = cand
-                else:
-                    groups.append([i])
-            return groups
-
-        def group(idx):
-            Tg = max(lens[i] for i in idx)
-            tab = (_lib.RowSamplingC * len(idx))(*[rows[i] for i in idx])
-            wtab = (_lib.RowWarpersC * len(idx))(*[warps[i] for i in idx]) if warps is not None else None
-            return emb[idx][:, T - Tg:], [Tg - lens[i] for i in idx], trail[idx], tab, wtab
+        def group(idx, spare=0):
+            """the requests `idx`, and `spare` spare rows behind them, as `stream_open` / `stream_admit` take a group"""
+            idx = idx + idx[:1] * spare
+            Tg = max(p.lens[i] for i in idx)
+            tab = (_lib.RowSamplingC * len(idx))(*[p.rows[i] for i in idx])
+            for k in range(len(idx) - spare, len(idx)):
+                tab[k].max_new_tokens, tab[k].min_new_tokens = 1, 0
+            wtab = (_lib.RowWarpersC * len(idx))(*[p.warp[i] for i in idx]) if p.warp is not None else None
+            return p.emb[idx][:, p.T - Tg:], [Tg - p.lens[i] for i in idx], p.trail[idx], tab, wtab
 
         with self._lock:
             caps0 = self.stats()["graph_captures"]
             try:
-                while queue:
-                    # a fresh stream: the longest prompt first, then the longest of the rest whose limits fit behind it
-                    T0 = lens[queue[0]]
-                    first = [i for i in queue if T0 + int(rows[i].max_new_tokens) <= self.max_seq][:mb]
-                    spare = 0
-                    if row_positions:
-                        # the ONE stream's width is its opening group's (an admission takes a row of the stream): open with the widest
-                        # group that fits, and bring the stream to full width with spare rows -- copies of the first prompt under the
-                        # limit 1, finished with their token 0 -- that the first admission fills
-                        first = self._widest_opener(queue, lens, [limit(i) for i in range(N)], self.max_seq, mb)
-                        spare = min(mb, N) - len(first)
-                        if pooled:        # the opening prompts (the spare rows' copies included) must fit the pool
-                            width = max(1, self.kv_pages // pages_of(max(lens[i] for i in first)))
-                            first = first[:width]
-                            spare = min(spare, width - len(first))
-                    queue = [i for i in queue if i not in first]
-                    e, npd, tr, tab, wtab = group(first + first[:1] * spare)
-                    for k in range(len(first), len(first) + spare):
-                        tab[k].max_new_tokens, tab[k].min_new_tokens = 1, 0
-                    codes, hidden = self.stream_open(e, npd, tr, pad, tab, max_row, eos, suppress_tokens, output_hidden_states, row_positions,
-                                                     warpers=wtab)
-                    st["streams"] += 1
-                    slot, seen, fresh = list(first) + [None] * spare, [0] * (len(first) + spare), set(first)
+                while pol.queue:
+                    e, npd, tr, tab, wtab = group(*pol.open_stream())
+                    codes, hidden = self.stream_open(e, npd, tr, p.pad, tab, p.max_new_tokens, p.eos, p.suppress, output_hidden_states,
+                                                     row_positions, warpers=wtab)
                     try:
-                        while any(r is not None for r in slot):
-                            if pooled:
-                                while True:
-                                    need, avail, used = step_need(slot, seen)
-                                    running = [b for b, r in enumerate(slot) if r is not None]
-                                    if need <= avail or len(running) <= 1:
-                                        break
-                                    victim = min(running, key=lambda b: (seen[b], -slot[b]))
-                                    self.stream_evict([victim])
-                                    queue.insert(0, slot[victim])
-                                    restarted.add(slot[victim])
-                                    fresh.discard(slot[victim])
-                                    slot[victim] = None
-                                    st["preemptions"] += 1
-                                st["peak_pages"] = max(st["peak_pages"], used)
+                        while pol.active:
+                            # (pooled: the engine's counts are read again after every eviction)
+                            while pol.pooled and (victim := pol.victim(*self.stream_kv()[:2], self.stream_row_lens())) is not None:
+                                self.stream_evict([victim])
                             self.stream_step(packet_frames)
                             unfinished, frames, kv_len = self.stream_rows()
-                            packet = []
-                            for b, r in enumerate(slot):
-                                if r is None:
-                                    continue
-                                done, k0, k1 = not unfinished[b], seen[b], frames[b]
-                                if k1 > k0 or done:
-                                    packet.append(RefillRow(request=r, row=b, codes=codes[b, k0:k1].clone(), first=r in fresh, last=done,
-                                                            hidden=hidden[b, k0:k1].clone() if hidden is not None else None,
-                                                            restart=r in fresh and r in restarted))
-                                    fresh.discard(r)
-                                    restarted.discard(r)
-                                    seen[b] = k1
-                                if done:
-                                    st["row_frames"] += k1
-                                    slot[b] = None
-                            yield RefillPacket(packet)
-                            free = [b for b, r in enumerate(slot) if r is None]
-                            if row_positions:
-                                take = admissible(free, len(slot) - len(free)) if pooled else queue[:len(free)]
-                                at = 0
-                                for grp in admission_groups(take):
-                                    e, npd, tr, tab, wtab = group(grp)
-                                    self.stream_admit(free[at:at + len(grp)], e, npd, tr, tab, warpers=wtab)
-                                    at += len(grp)
-                            else:
-                                take = [i for i in queue if lens[i] <= kv_len and kv_len + limit(i) <= self.max_seq][:len(free)]
-                                if take:
-                                    e, npd, tr, tab, wtab = group(take)
-                                    self.stream_admit(free[:len(take)], e, npd, tr, tab, warpers=wtab)
-                            if take:
-                                for b, r in zip(free, take):
-                                    slot[b], seen[b] = r, 0
-                                    fresh.add(r)
-                                queue = [i for i in queue if i not in take]
+                            yield RefillPacket([RefillRow(request=r.request, row=r.row, codes=codes[r.row, r.k0:r.k1].clone(), first=r.first,
+                                                          last=r.last, restart=r.restart,
+                                                          hidden=hidden[r.row, r.k0:r.k1].clone() if hidden is not None else None)
+                                                for r in pol.reports(unfinished, frames)])
+                            for row_ids, grp in pol.admissions(kv_len, self.stream_kv()[1] if pol.tight else None):
+                                e, npd, tr, tab, wtab = group(grp)
+                                self.stream_admit(row_ids, e, npd, tr, tab, warpers=wtab)
                     finally:
-                        s1 = self.stats()
-                        st["admit_calls"] += s1["admit_calls"]
-                        st["admitted_rows"] += s1["admitted_rows"]
-                        st["max_row_len"] = max(st["max_row_len"], s1["max_row_len"]) if row_positions else 0
-                        st["frames_run"] += self.stream_close()
+                        pol.stream_closed(self.stats(), self.stream_close())
             finally:
-                st["graph_captures"] = self.stats()["graph_captures"] - caps0
-                st["occupancy"] = st["row_frames"] / max(1, st["frames_run"] * mb)
-                self.last_refill = st
+                self.last_refill = pol.finish(self.stats()["graph_captures"] - caps0)
 
-    @staticmethod
-    def _widest_opener(queue, lens, limits, max_seq, max_batch):
-        """The opening group of a stream with per-row positions: among the groups {requests no longer than T whose limit fits behind T}
-        for every prompt length T, the one with the most members (at most max_batch, longest prompts first; ties go to the longer T).
-        `queue` is sorted longest first.  Limits clamped to the room their own prompt leaves (`_clamp_new_tokens`) fit only behind
-        their own length, so the group can be narrow: the scheduler fills the stream's other rows with spare rows."""
-        best = []
-        for T in sorted({lens[i] for i in queue}, reverse=True):
-            cand = [i for i in queue if lens[i] <= T and T + limits[i] <= max_seq][:max_batch]
-            if len(cand) > len(best):
-                best = cand
-        return best
+    _widest_opener = staticmethod(widest_opener)
 
-    def _generate_refill(self, inputs_embeds: torch.Tensor, attention_mask: torch.Tensor, trailing_text_hidden: torch.Tensor,
-                         tts_pad_embed: torch.Tensor, max_new_tokens=2048, min_new_tokens=2, do_sample=True, top_k=50, top_p=1.0,
-                         temperature=0.9, subtalker_dosample=True, subtalker_top_k=50, subtalker_top_p=1.0, subtalker_temperature=0.9,
-                         eos_token_id: Optional[int] = None, repetition_penalty=1.05, suppress_tokens: Optional[List[int]] = None,
-                         output_hidden_states: bool = True, seed=None, packet_frames: int = 4, row_positions: bool = False,
-                         min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None, no_repeat_ngram_size=None,
-                         **unused) -> TalkerGenerateOutput:
+    def _generate_refill(self, inputs_embeds: torch.Tensor, *args, eos_token_id: Optional[int] = None, output_hidden_states: bool = True,
+                         **kw) -> TalkerGenerateOutput:
         """`generate(..., schedule="refill")`: the packets of `_refill_stream` (its arguments and schedule) collected per request.
         Returns the requests in the order given, in `generate`'s structure: codes (N, F, G) with eos in codebook 0 behind a request's
         last frame, tokens (N, F + 1)."""
@@ -1016,14 +820,7 @@ class TalkerEngine:
         eos = c.codec_eos_token_id if eos_token_id is None else int(eos_token_id)
         N, G, H = int(inputs_embeds.shape[0]), c.num_code_groups, c.hidden_size
         parts, hparts = [[] for _ in range(N)], [[] for _ in range(N)]
-        for packet in self._refill_stream(inputs_embeds, attention_mask, trailing_text_hidden, tts_pad_embed, max_new_tokens=max_new_tokens,
-                                          min_new_tokens=min_new_tokens, do_sample=do_sample, top_k=top_k, top_p=top_p,
-                                          temperature=temperature, subtalker_dosample=subtalker_dosample, subtalker_top_k=subtalker_top_k,
-                                          subtalker_top_p=subtalker_top_p, subtalker_temperature=subtalker_temperature, eos_token_id=eos,
-                                          repetition_penalty=repetition_penalty, suppress_tokens=suppress_tokens,
-                                          output_hidden_states=output_hidden_states, seed=seed, packet_frames=packet_frames,
-                                          row_positions=row_positions, min_p=min_p, typical_p=typical_p, epsilon_cutoff=epsilon_cutoff,
-                                          eta_cutoff=eta_cutoff, no_repeat_ngram_size=no_repeat_ngram_size):
+        for packet in self._refill_stream(inputs_embeds, *args, eos_token_id=eos, output_hidden_states=output_hidden_states, **kw):
             for e in packet.rows:
                 if e.restart:         # a preempted request starts again at frame 0: what it had delivered is replayed
                     parts[e.request], hparts[e.request] = [], []
