@@ -58,7 +58,8 @@ const char* qtts_last_error(void);
  * needs the new calls finds out by looking the symbols up; still 15: + qtts_row_warpers, qtts_talker_set_row_warpers,
  * qtts_talker_sampler_class -- a new struct and two entry points, no existing signature or struct changed; still 15:
  * + qtts_codec_stream_prime_rows, qtts_codec_stream_prime_tail -- two entry points added, no signature and no struct changed; a binding
- * that needs them finds out by looking the symbols up). */
+ * that needs them finds out by looking the symbols up; still 15: + qtts_row_processors, qtts_talker_set_row_processors -- a new
+ * struct and one entry point, no existing signature or struct changed). */
 #define QTTS_ABI_VERSION 15
 int qtts_abi_version(void);
 
@@ -598,6 +599,56 @@ typedef struct qtts_row_warpers {      /* 32 bytes; 0 = off for every field */
 } qtts_row_warpers;
 int qtts_talker_set_row_warpers(qtts_talker* t, const qtts_row_warpers* rows_host, int32_t n_rows);
 int qtts_talker_sampler_class(qtts_talker* t, int32_t* talker_host, int32_t* subtalker_host);
+
+/* The remaining HF logits processors of the talker's codebook-0 sampler, per request (a struct and an entry point added under ABI 15;
+ * nothing existing changed): sequence_bias, bad_words_ids, forced_eos_token_id, exponential_decay_length_penalty and
+ * begin_suppress_tokens (transformers generation/logits_process.py; min_length is folded into the row's min_new_tokens by the caller).
+ * With them the chain of a row's token is, in `_get_logits_processor` order,
+ *   SequenceBias -> RepetitionPenalty -> NoRepeatNGram -> NoBadWords -> MinLength / MinNewTokensLength -> ForcedEOS ->
+ *   ExponentialDecayLengthPenalty -> SuppressTokens -> SuppressTokensAtBegin ->
+ *   [Temperature -> TopK -> TopP -> MinP -> Typical -> EpsilonCutoff -> EtaCutoff] -> argmax | softmax + draw.
+ * cur_len is the row's own generated count, counted from the row's origin; EOS is the call's eos_token_id.
+ *   records       n_words words holding n_records ragged records {kind, len, bias (float bits), tokens[len]}:
+ *                 QTTS_PROC_KIND_BIAS   a single token is biased at every step; a longer sequence biases its LAST token when the row
+ *                                       has generated at least len tokens and its last len - 1 equal the sequence's first len - 1.
+ *                                       Biases that land on one token are summed in fp32 -- single-token records first, then the
+ *                                       others in listed order, as HF does -- and the sum is added to the score;
+ *                 QTTS_PROC_KIND_BAN    the same match, the token becomes -inf (behind the n-gram ban; `bias` is ignored);
+ *                 QTTS_PROC_KIND_BEGIN  every listed token is -inf at the row's own step 0 only.
+ *   flags         QTTS_PROC_DECAY: once cur_len > decay_start, x[eos] += |x[eos]| * (decay_factor ** (cur_len - decay_start) - 1) -- the
+ *                 power in double ON THE DEVICE (one thread), the product and the sum in fp32, as HF evaluates them; an EOS score
+ *                 that is already -inf stays -inf (HF: NaN).  QTTS_PROC_FORCED_EOS: at cur_len == limit - 1 every score becomes -inf and
+ *                 EOS 0, where limit is the row's max_new_tokens as qtts_row_sampling holds it; it comes after the EOS floor, so it
+ *                 wins over min_new_tokens.
+ *   capacity      at most QTTS_PROC_MAX_RECORDS records and QTTS_PROC_MAX_TOKENS tokens per row; more is QTTS_ERR_LIMIT, the
+ *                 message naming the row and the cap.  A kind, a length < 1, a token id outside [0, vocab), a non-finite
+ *                 decay_factor or one <= 0, records that overrun n_words: QTTS_ERR_ARG, naming the row.
+ *   set_row_processors  ONE-SHOT and consumed exactly like qtts_talker_set_row_warpers (above), by the same calls, with the same count
+ *                 rule; a scalar qtts_talker_generate / qtts_talker_stream_begin with a table pending is refused and the table
+ *                 dropped; NULL / 0 clears.  Both tables may be pending together.  The entries live in a third device table of fixed
+ *                 capacity per row: their VALUES are not part of the captured frame graph.  A table with any control on makes the
+ *                 talker's sampler sample_warp_kernel (class 3) -- the same monotone graph-key flag as the warpers', so the first such
+ *                 occupant admitted into a stream that ran in another class re-captures once and values never do.  A row admitted
+ *                 without a table gets an all-off entry; a table with everything off is exactly the call without it.  Teacher
+ *                 forcing refuses the table call as before. */
+#define QTTS_PROC_MAX_RECORDS 96
+#define QTTS_PROC_MAX_TOKENS 512
+#define QTTS_PROC_MAX_WORDS (3 * QTTS_PROC_MAX_RECORDS + QTTS_PROC_MAX_TOKENS)
+#define QTTS_PROC_KIND_BIAS 1
+#define QTTS_PROC_KIND_BAN 2
+#define QTTS_PROC_KIND_BEGIN 3
+#define QTTS_PROC_DECAY 1
+#define QTTS_PROC_FORCED_EOS 2
+typedef struct qtts_row_processors {   /* 32 + 4 x QTTS_PROC_MAX_WORDS bytes; all zero = everything off */
+    double decay_factor;
+    int32_t decay_start;
+    int32_t flags;
+    int32_t n_records;
+    int32_t n_words;
+    int32_t reserved[2];
+    int32_t records[QTTS_PROC_MAX_WORDS];
+} qtts_row_processors;
+int qtts_talker_set_row_processors(qtts_talker* t, const qtts_row_processors* rows_host, int32_t n_rows);
 
 /* Test/diagnostic hooks (device -> caller device buffers, after prefill / a generate call). */
 int qtts_talker_debug_logits(qtts_talker* t, float* logits_dev /* (B, vocab) */, void* stream);

@@ -61,6 +61,20 @@ class RowWarpersC(C.Structure):
                 ("no_repeat_ngram_size", C.c_int32), ("reserved", C.c_int32 * 3)]
 
 
+# include/qtts.h QTTS_PROC_*: the capacity of one row's processors and the record kinds / flags
+PROC_MAX_RECORDS, PROC_MAX_TOKENS = 96, 512
+PROC_MAX_WORDS = 3 * PROC_MAX_RECORDS + PROC_MAX_TOKENS
+PROC_KIND_BIAS, PROC_KIND_BAN, PROC_KIND_BEGIN = 1, 2, 3
+PROC_DECAY, PROC_FORCED_EOS = 1, 2
+
+
+class RowProcessorsC(C.Structure):
+    """include/qtts.h qtts_row_processors: one request's remaining HF logits processors (qtts_talker_set_row_processors); all zero = off.
+    `records`: n_records ragged {kind, len, bias (float bits), tokens[len]} in n_words words."""
+    _fields_ = [("decay_factor", C.c_double), ("decay_start", C.c_int32), ("flags", C.c_int32), ("n_records", C.c_int32),
+                ("n_words", C.c_int32), ("reserved", C.c_int32 * 2), ("records", C.c_int32 * PROC_MAX_WORDS)]
+
+
 class EncoderConfigC(C.Structure):
     _fields_ = [("hidden_size", C.c_int32), ("num_filters", C.c_int32), ("num_residual_layers", C.c_int32),
                 ("n_ratios", C.c_int32), ("ratios", C.c_int32 * 8), ("kernel_size", C.c_int32), ("last_kernel_size", C.c_int32),
@@ -118,7 +132,7 @@ SYMBOLS = ["qtts_last_error", "qtts_abi_version", "qtts_set_option", "qtts_get_o
            "qtts_talker_stream_begin_admitting", "qtts_talker_stream_admit", "qtts_talker_stream_rows",
            "qtts_talker_stream_begin_admitting_rows", "qtts_talker_stream_row_lens", "qtts_talker_stream_mode",
            "qtts_talker_set_kv_pool", "qtts_talker_stream_kv", "qtts_talker_stream_evict",
-           "qtts_talker_set_row_warpers", "qtts_talker_sampler_class",
+           "qtts_talker_set_row_warpers", "qtts_talker_sampler_class", "qtts_talker_set_row_processors",
            "qtts_talker_debug_logits", "qtts_talker_debug_kv_table", "qtts_talker_debug_cp_logits", "qtts_talker_get_stats", "qtts_talker_get_gemm_profile", "qtts_talker_set_teacher",
            "qtts_talker_set_profile"]
 
@@ -221,6 +235,7 @@ def load_library():
     lib.qtts_talker_stream_evict.argtypes = [vp, i32, C.POINTER(C.c_int32)]
     lib.qtts_talker_debug_kv_table.argtypes = [vp, i32, C.POINTER(C.c_int32), vp]
     lib.qtts_talker_set_row_warpers.argtypes = [vp, C.POINTER(RowWarpersC), i32]
+    lib.qtts_talker_set_row_processors.argtypes = [vp, C.POINTER(RowProcessorsC), i32]
     lib.qtts_talker_sampler_class.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     lib.qtts_talker_stream_admit.argtypes = [vp, i32, C.POINTER(C.c_int32), f32p, i32, C.POINTER(C.c_int32), f32p, i32,
                                              C.POINTER(RowSamplingC), vp]

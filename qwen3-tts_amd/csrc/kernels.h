@@ -428,9 +428,27 @@ struct RowWarpers {
 static_assert(sizeof(RowWarpers) == 32, "sampling.hip: sample_warp_kernel reads an entry as two 16-byte blocks");
 // The talker's launch of a table whose rows use any of them: the row's whole chain -- greedy rows, any top_k, top_p -- in one kernel.
 // `s`: table mode, talker half (rows set, rows_sub == 0).
+// One request's remaining HF logits processors (qtts_row_processors, include/qtts.h) as sample_warp_kernel reads them: entry b of a
+// third table beside rows[b] and warp[b], fixed capacity per row (its values never enter a captured graph).  A 32-byte header, then
+// the records -- the ABI's ragged {kind, len, bias, tokens[len]} with the tokens moved into a pool, so that thread r finds record r
+// without walking the list.  Bias records of one token come first, the others in listed order: the order HF adds them in.
+constexpr int PROC_MAX_RECORDS = 96;         // = QTTS_PROC_MAX_RECORDS
+constexpr int PROC_MAX_TOKENS = 512;         // = QTTS_PROC_MAX_TOKENS
+enum { PROC_BIAS = 1, PROC_BAN = 2, PROC_BEGIN = 3 };                                             // = QTTS_PROC_KIND_*
+enum { PROCF_DECAY = 1, PROCF_FORCED_EOS = 2, PROCF_HAS_BIAS = 4, PROCF_HAS_BAN = 8, PROCF_HAS_BEGIN = 16 };
+struct RowProcRec { int kind; int len; float bias; int off; };    // tokens tok[off .. off + len)
+struct RowProcessors {
+    int flags; int n_rec; int decay_start; int pad0;
+    double decay_factor; int pad1, pad2;
+    RowProcRec rec[PROC_MAX_RECORDS];
+    int tok[PROC_MAX_TOKENS];
+};
+static_assert(sizeof(RowProcRec) == 16 && offsetof(RowProcessors, decay_factor) == 16 && offsetof(RowProcessors, rec) == 32 &&
+              sizeof(RowProcessors) % 16 == 0, "sampling.hip: sample_warp_kernel reads the header and a record as 16-byte blocks");
 struct SampleWarpParams {
     SampleParams s;
     const RowWarpers* warp;                  // [B] device
+    const RowProcessors* proc;               // [B] device (an all-zero entry: everything off)
 };
 void launch_sample_warp(const SampleWarpParams& p, hipStream_t st);
 

@@ -740,10 +740,18 @@ void launch_sample(const SampleParams& p, hipStream_t st) {
 
 // ---------------------------------------------------------------------------------- the remaining HF warpers + the n-gram ban
 // The talker's sampler of a table in which any row uses min_p, typical_p, epsilon_cutoff, eta_cutoff or no_repeat_ngram_size
-// (qtts_row_warpers).  One row's whole chain, transformers 4.57.3 `_get_logits_processor` order:
-//   RepetitionPenalty -> NoRepeatNGram -> MinNewTokensLength -> SuppressTokens ->
+// (qtts_row_warpers), or any row has a qtts_row_processors control on.  One row's whole chain, transformers `_get_logits_processor`
+// order (4.57.3 and 5.x agree on it):
+//   SequenceBias -> RepetitionPenalty -> NoRepeatNGram -> NoBadWords -> MinLength / MinNewTokensLength -> ForcedEOS ->
+//   ExponentialDecayLengthPenalty -> SuppressTokens -> SuppressTokensAtBegin ->
 //   [Temperature -> TopK -> TopP -> MinP -> Typical -> EpsilonCutoff -> EtaCutoff] -> argmax | softmax + draw
-// for any combination of knobs (greedy rows skip the bracket, as HF does, and keep the ban).  Entry discipline of sample_kernel_v2:
+// for any combination of knobs (greedy rows skip the bracket, as HF does, and keep everything in front of it).  The stages of
+// qtts_row_processors read the row's entry of a third table (RowProcessors, kernels.h): a header and up to PROC_MAX_RECORDS records
+// {kind, len, bias, off} over a pool of tokens.  Record r is matched by thread r against the row's history; the biases of the records
+// that match are added in RECORD order by the one thread that owns the token (v & 255 == tid), so the sum does not depend on thread
+// or wave scheduling; bans are flags like the n-gram ban's.  A row with nothing of it on skips every such stage on a uniform branch.
+// The decay's power is evaluated in double by the one thread that owns EOS (HF: Python's pow), the product and the sum in fp32
+// without contraction (HF: two fp32 tensor operations).  Entry discipline of sample_kernel_v2:
 // every independent load before the early exit, the thread's own V / 256 logits in registers (v = it * 256 + tid).  No sort: every
 // cut is a threshold.  TopK / TopP / Typical find theirs by a bit-by-bit selection over float_key -- 32 block reductions of a count or
 // of probability mass, one barrier each (partials double-buffered by round parity); MinP / Epsilon / Eta compare softmax numerators
@@ -752,6 +760,13 @@ void launch_sample(const SampleParams& p, hipStream_t st) {
 // removes the maximum except Typical, after which the maximum is taken again.  The inverse-CDF scan runs in sample_kernel's order
 // for the row's own top_k (slot order (wave, slice, lane) for 0 < top_k <= 256, else index order), so a row without any of the new
 // knobs draws sample_kernel's token for the same u (up to rounding in the scan).  No finite score left: token 0.
+// ExponentialDecayLengthPenalty on the EOS score: scores + |scores| * (pow - 1), two fp32 roundings as in torch (never one fma)
+__device__ __forceinline__ float decay_eos(float x, float mul) {
+#pragma clang fp contract(off)
+    const float pen = fabsf(x) * mul;
+    return x + pen;
+}
+
 template <int EPT>
 __global__ __launch_bounds__(256) void sample_warp_kernel(SampleWarpParams pw) {
     __shared__ float sc[EPT * 256];
@@ -761,6 +776,9 @@ __global__ __launch_bounds__(256) void sample_warp_kernel(SampleWarpParams pw) {
     __shared__ __attribute__((aligned(16))) float scan[256];
     __shared__ int pick_lo, pick_hi;
     __shared__ int wpick[4], wlast[4];
+    __shared__ int ptok[PROC_MAX_RECORDS];                  // record r's token when its sequence matches the history's end, else -1
+    __shared__ float pbias[PROC_MAX_RECORDS];
+    __shared__ int beg_eos;                                 // EOS is among the tokens suppressed at the row's step 0
 
     QTTS_TS_BEGIN();
     const SampleParams& p = pw.s;
@@ -774,6 +792,10 @@ __global__ __launch_bounds__(256) void sample_warp_kernel(SampleWarpParams pw) {
     const RowKnobs kn = row_knobs(p, b);
     const uint4* we = reinterpret_cast<const uint4*>(pw.warp + b);
     const uint4 wa = we[0], wb = we[1];
+    const uint4* pe = reinterpret_cast<const uint4*>(pw.proc + b);     // the row's processors: the header and record `tid` (the table has its full capacity)
+    const uint4 pa = pe[0];
+    const double decay_factor = pw.proc[b].decay_factor;
+    const uint4 prec = pe[2 + (tid < PROC_MAX_RECORDS ? tid : 0)];
     const int n_gen = p.n_generated_dev ? n_gen_s - kn.origin : 0;      // the ROW's token count and step (sample_kernel)
     const int n_hist = min(n_gen, p.gen_stride);
     const uint32_t step = p.step_dev ? (uint32_t)(step_s - kn.origin) : 0u;
@@ -791,6 +813,22 @@ __global__ __launch_bounds__(256) void sample_warp_kernel(SampleWarpParams pw) {
     QTTS_TS_DRAINED(1);                    // (tstamp build: phases 1..5 = logits arrived | processors | cuts | drawn | rows gathered)
     const float min_p = __uint_as_float(wa.x), typical_p = __uint_as_float(wa.y), eps_cut = __uint_as_float(wa.z), eta_cut = __uint_as_float(wa.w);
     const int ngram = (int)wb.x;
+    const int pflags = (int)pa.x, n_rec = min((int)pa.y, PROC_MAX_RECORDS), decay_start = (int)pa.z;
+    const int* hist = p.generated ? p.generated + (size_t)b * p.gen_stride : nullptr;
+    const int* ptoks = pw.proc[b].tok;
+    const int rkind = tid < n_rec ? (int)prec.x : 0, rlen = (int)prec.y, roff = (int)prec.w;
+    // whether this thread's record applies now: a single token always; a longer sequence when the history holds at least as many tokens
+    // as the sequence (HF ignores it before that) and ends in the sequence's first len - 1 (read from global memory: a suffix may lie
+    // anywhere, also past the 256 prefetched entries)
+    auto seq_match = [&]() -> bool {
+        const int np = rlen - 1;
+        if (np == 0) return true;
+        if (!hist || rlen > n_hist) return false;
+        bool m = true;
+#pragma unroll 4
+        for (int j = 0; j < np; ++j) m = m && hist[n_hist - np + j] == ptoks[roff + j];
+        return m;
+    };
 
     int par = 0;                           // parity of the next block reduction (the partials' buffer)
     auto bsum = [&](float v) -> float {
@@ -810,12 +848,32 @@ __global__ __launch_bounds__(256) void sample_warp_kernel(SampleWarpParams pw) {
         return r;
     };
 
-    // ---- 1. RepetitionPenalty and NoRepeatNGram: both are scatters over the row's history -> flags in LDS
+    // ---- 0b. SequenceBias: the matching records' biases, summed per token in record order by the token's owner, then added
+    if (pflags & PROCF_HAS_BIAS) {
+#pragma unroll
+        for (int it = 0; it < EPT; ++it) sc[it * 256 + tid] = 0.f;
+        if (tid < PROC_MAX_RECORDS) {
+            const bool on = rkind == PROC_BIAS && seq_match();
+            ptok[tid] = on ? ptoks[roff + rlen - 1] : -1;
+            pbias[tid] = __uint_as_float(prec.z);
+        }
+        __syncthreads();
+        for (int r = 0; r < n_rec; ++r) {
+            const int tk = ptok[r];
+            if (tk >= 0 && tk < V && (tk & 255) == tid) sc[tk] += pbias[r];
+        }
+#pragma unroll
+        for (int it = 0; it < EPT; ++it) x[it] += sc[it * 256 + tid];      // (entries of `sc` this thread alone has touched: no barrier)
+    }
+    // ---- 1. RepetitionPenalty, NoRepeatNGram and NoBadWords (+ the begin suppression's flags): scatters over the row's history -> flags in LDS
     const bool want_rep = p.generated && kn.rep != 1.0f;
     const bool want_ban = p.generated && ngram > 0 && n_hist >= ngram;     // (fewer than n tokens: no n-gram exists yet)
-    if (want_rep || want_ban) {
+    const bool want_begin = (pflags & PROCF_HAS_BEGIN) && n_gen == 0;
+    const bool want_bw = (pflags & PROCF_HAS_BAN) || want_begin;
+    if (want_rep || want_ban || want_bw) {
 #pragma unroll
         for (int it = 0; it < EPT; ++it) { sc[it * 256 + tid] = 0.f; ban[it * 256 + tid] = 0; }
+        if (tid == 0) beg_eos = 0;
         __syncthreads();
         const int* h = p.generated + (size_t)b * p.gen_stride;
         if (want_rep) {
@@ -841,6 +899,19 @@ __global__ __launch_bounds__(256) void sample_warp_kernel(SampleWarpParams pw) {
                 }
             }
         }
+        if (want_bw) {
+            if (rkind == PROC_BAN && seq_match()) {
+                const int tok = ptoks[roff + rlen - 1];
+                if (tok >= 0 && tok < V) ban[tok] = 1;
+            } else if (rkind == PROC_BEGIN && want_begin) {
+                // (applied with the other bans: a ban commutes with everything up to ForcedEOS, which only EOS survives -- beg_eos)
+                for (int j = 0; j < rlen; ++j) {
+                    const int tok = ptoks[roff + j];
+                    if (tok >= 0 && tok < V) ban[tok] = 1;
+                    if (tok == p.eos) beg_eos = 1;
+                }
+            }
+        }
         __syncthreads();
 #pragma unroll
         for (int it = 0; it < EPT; ++it) {
@@ -850,12 +921,33 @@ __global__ __launch_bounds__(256) void sample_warp_kernel(SampleWarpParams pw) {
         }
         __syncthreads();                                     // flags consumed before `sc` is written again
     }
-    // ---- 2. MinNewTokensLength, SuppressTokens
+    // ---- 2. MinLength / MinNewTokensLength (one floor), ForcedEOS, ExponentialDecayLengthPenalty, SuppressTokens, SuppressTokensAtBegin
     const bool block_eos = p.eos >= 0 && n_gen < kn.min_new;
+    if (pflags & (PROCF_DECAY | PROCF_FORCED_EOS)) {
+        // the row's limit is its max_new_tokens as the table holds it (after the host's clamp to max_seq)
+        const bool forced_now = (pflags & PROCF_FORCED_EOS) && p.eos >= 0 && n_gen == kn.limit - 1;
+        const bool decay_now = (pflags & PROCF_DECAY) && p.eos >= 0 && n_gen > decay_start;
+        const bool beg_kill = forced_now && want_begin && beg_eos != 0;
+        float dmul = 0.f;
+        if (decay_now && tid == (p.eos & 255)) {
+            dmul = (float)(pow(decay_factor, (double)(n_gen - decay_start)) - 1.0);
+        }
+#pragma unroll
+        for (int it = 0; it < EPT; ++it) {
+            const int v = it * 256 + tid;
+            float xv = x[it];
+            if (block_eos && v == p.eos) xv = -INFINITY;
+            if (forced_now) xv = v == p.eos ? 0.f : -INFINITY;
+            if (decay_now && v == p.eos && xv != -INFINITY) xv = decay_eos(xv, dmul);   // (HF turns an EOS of -inf into NaN here)
+            if (sup[it] || (beg_kill && v == p.eos)) xv = -INFINITY;
+            x[it] = xv;
+        }
+    } else {
 #pragma unroll
     for (int it = 0; it < EPT; ++it) {
         const int v = it * 256 + tid;
         if ((block_eos && v == p.eos) || sup[it]) x[it] = -INFINITY;
+    }
     }
     QTTS_TS(2);
 
@@ -1083,7 +1175,7 @@ __global__ __launch_bounds__(256) void sample_warp_kernel(SampleWarpParams pw) {
 
 void launch_sample_warp(const SampleWarpParams& p, hipStream_t st) {
     QTTS_REQUIRE(p.s.V <= SAMPLE_MAX_V, QTTS_ERR_LIMIT, "sample: vocab too large");
-    QTTS_REQUIRE(p.s.rows && !p.s.rows_sub && p.warp, QTTS_ERR_ARG, "sample_warp: the talker's launch of a per-row table only");
+    QTTS_REQUIRE(p.s.rows && !p.s.rows_sub && p.warp && p.proc, QTTS_ERR_ARG, "sample_warp: the talker's launch of a per-row table only");
     if (p.s.V <= 2048) hipLaunchKernelGGL(sample_warp_kernel<8>, dim3(p.s.B), dim3(256), 0, st, p);
     else if (p.s.V <= 3072) hipLaunchKernelGGL(sample_warp_kernel<12>, dim3(p.s.B), dim3(256), 0, st, p);
     else if (p.s.V <= 4096) hipLaunchKernelGGL(sample_warp_kernel<16>, dim3(p.s.B), dim3(256), 0, st, p);

@@ -128,6 +128,12 @@ struct qtts_talker {
     bool row_warp_t = false;
     std::vector<RowWarpers> warp_pending;
     bool warp_pending_set = false;
+    // the rows' remaining logits processors (qtts_talker_set_row_processors): a third table of max_batch entries of fixed capacity, zero
+    // (everything off) at creation.  A row with one on makes the table's class sample_warp_kernel's too (row_warp_t).  `proc_dirty`: the
+    // device table may hold an entry that is not all zero -- a call or an admission without processors then clears its rows.
+    DevBuf proc_d;
+    std::vector<RowProcessors> proc_pending;
+    bool proc_pending_set = false, proc_dirty = false;
     int64_t graph_captures = 0;        // frame-graph captures over the engine's life
     // resumable generation (qtts_talker_stream_*): everything a later call needs to keep stepping the same request
     struct StreamGen {
@@ -1048,6 +1054,8 @@ void qtts_talker::finalize() {
         QTTS_CHECK_HIP(hipMemset(cp_hid.p, 0, cp_hid.bytes));
     }
     n_pad_d.alloc(R * 4); suppress.alloc(c.vocab_size); seed_d.alloc(8); rows_d.alloc((size_t)R * sizeof(SampleRow)); warp_d.alloc((size_t)R * sizeof(RowWarpers));
+    proc_d.alloc((size_t)R * sizeof(RowProcessors));
+    QTTS_CHECK_HIP(hipMemset(proc_d.p, 0, (size_t)R * sizeof(RowProcessors)));
     QTTS_CHECK_HIP(hipMemset(ss_rows.p, 0, ss_rows.bytes));
     int* ip = ints.as<int>();
     row_len_p = ip + 64 + 64;
@@ -1191,7 +1199,7 @@ void qtts_talker::sample_talker(const qtts_sampling& sp, int eos, int min_new, i
     p.max_new_tokens = max_new; p.done_in = ss.done;
     if (row_mode) { p.rows = rows_d.as<SampleRow>(); p.rows_sub = 0; p.rows_fast = row_fast_t; }
     if (tf.codes && tf.trace) launch_teacher(teacher_params(), 0, st);
-    if (row_mode && row_warp_t) { SampleWarpParams pw{p, warp_d.as<RowWarpers>()}; launch_sample_warp(pw, st); }
+    if (row_mode && row_warp_t) { SampleWarpParams pw{p, warp_d.as<RowWarpers>(), proc_d.as<RowProcessors>()}; launch_sample_warp(pw, st); }
     else launch_sample(p, st);
     launch_sample_finish(ss, B, max_new, st);
     if (tf.codes) launch_teacher(teacher_params(), 1, st);
@@ -1439,7 +1447,8 @@ struct RowTable {
     int poll_from = 0x7fffffff; // no row can finish before this many tokens exist (EOS blocked and limit not reached): no poll needed earlier
     bool fast_t = true, fast_c = true;      // every row meets sample_kernel_v2's predicate, talker / subtalker half (launch_sample)
     std::vector<RowWarpers> wtab;           // the rows' warpers (all off without a pending qtts_talker_set_row_warpers table)
-    bool warp = false;                      // some row has one on: the talker's sampler is sample_warp_kernel
+    bool warp = false;                      // some row has one on (or a processor, below): the talker's sampler is sample_warp_kernel
+    std::vector<RowProcessors> ptab;        // the rows' processors; empty: none on (no pending qtts_talker_set_row_processors table, or all off)
 };
 // one request's warpers, checked, as sample_warp_kernel reads them (`b`: the row the messages name); typical_p = 1 is stored as off
 static RowWarpers check_warpers(const qtts_row_warpers& q, int b, const char* who) {
@@ -1458,6 +1467,63 @@ static RowWarpers check_warpers(const qtts_row_warpers& q, int b, const char* wh
 static bool warpers_on(const RowWarpers& o) {
     return o.min_p > 0.0f || o.typical_p > 0.0f || o.epsilon_cutoff > 0.0f || o.eta_cutoff > 0.0f || o.no_repeat_ngram_size > 0;
 }
+// one request's processors, checked, as sample_warp_kernel reads them (`b`: the row the messages name): the ragged records become the
+// directory + token pool of RowProcessors, single-token bias records first (HF adds those first), everything else in listed order
+static RowProcessors check_processors(const qtts_row_processors& q, int b, int V, const char* who) {
+    auto fail = [&](int code, const std::string& what) { throw Error(code, std::string(who) + ": row " + std::to_string(b) + ": " + what); };
+    if (q.flags & ~(QTTS_PROC_DECAY | QTTS_PROC_FORCED_EOS)) fail(QTTS_ERR_ARG, "unknown flag");
+    if ((q.flags & QTTS_PROC_DECAY) && !(q.decay_factor > 0.0 && std::isfinite(q.decay_factor))) fail(QTTS_ERR_ARG, "decay_factor must be a finite value > 0");
+    if (q.n_records < 0 || q.n_words < 0) fail(QTTS_ERR_ARG, "n_records >= 0 and n_words >= 0");
+    if (q.n_records > QTTS_PROC_MAX_RECORDS)
+        fail(QTTS_ERR_LIMIT, std::to_string(q.n_records) + " records exceed the capacity of " + std::to_string(QTTS_PROC_MAX_RECORDS) + " per row");
+    if (q.n_words > QTTS_PROC_MAX_WORDS)
+        fail(QTTS_ERR_LIMIT, std::to_string(q.n_words) + " words exceed the capacity of " + std::to_string(QTTS_PROC_MAX_WORDS) + " per row");
+    RowProcessors o;
+    memset(&o, 0, sizeof(o));
+    o.flags = q.flags; o.decay_start = q.decay_start; o.decay_factor = (q.flags & QTTS_PROC_DECAY) ? q.decay_factor : 0.0;
+    int n_tok = 0;
+    for (int pass = 0; pass < 2; ++pass) {           // pass 0: single-token bias records; pass 1: the rest
+        int w = 0;
+        for (int r = 0; r < q.n_records; ++r) {
+            if (w + 3 > q.n_words) fail(QTTS_ERR_ARG, "record " + std::to_string(r) + " overruns n_words");
+            const int kind = q.records[w], len = q.records[w + 1];
+            if (kind != QTTS_PROC_KIND_BIAS && kind != QTTS_PROC_KIND_BAN && kind != QTTS_PROC_KIND_BEGIN) fail(QTTS_ERR_ARG, "record " + std::to_string(r) + ": unknown kind");
+            if (len < 1) fail(QTTS_ERR_ARG, "record " + std::to_string(r) + ": len >= 1");
+            if (len > q.n_words - w - 3) fail(QTTS_ERR_ARG, "record " + std::to_string(r) + " overruns n_words");
+            const bool first = kind == QTTS_PROC_KIND_BIAS && len == 1;
+            if (first == (pass == 0)) {
+                if (n_tok + len > QTTS_PROC_MAX_TOKENS)
+                    fail(QTTS_ERR_LIMIT, "the records' tokens exceed the capacity of " + std::to_string(QTTS_PROC_MAX_TOKENS) + " per row");
+                RowProcRec& e = o.rec[o.n_rec++];
+                e.kind = kind; e.len = len; e.off = n_tok;
+                memcpy(&e.bias, &q.records[w + 2], 4);
+                for (int j = 0; j < len; ++j) {
+                    const int tok = q.records[w + 3 + j];
+                    if (tok < 0 || tok >= V)
+                        fail(QTTS_ERR_ARG, "record " + std::to_string(r) + ": token " + std::to_string(tok) + " outside the vocabulary (" + std::to_string(V) + ")");
+                    o.tok[n_tok++] = tok;
+                }
+                o.flags |= kind == QTTS_PROC_KIND_BIAS ? PROCF_HAS_BIAS : (kind == QTTS_PROC_KIND_BAN ? PROCF_HAS_BAN : PROCF_HAS_BEGIN);
+            }
+            w += 3 + len;
+        }
+    }
+    return o;
+}
+static bool processors_on(const RowProcessors& o) { return o.flags != 0; }
+// The pending processor table, taken like the warper table (take_warpers): `set` says whether one was pending at all.
+static std::vector<RowProcessors> take_processors(qtts_talker* t, bool& set) {
+    std::vector<RowProcessors> w;
+    set = t->proc_pending_set;
+    w.swap(t->proc_pending);
+    t->proc_pending_set = false;
+    return w;
+}
+static void check_processor_count(const std::vector<RowProcessors>& w, bool set, int n, const char* who) {
+    if (set && (int)w.size() != n)
+        throw Error(QTTS_ERR_ARG, std::string(who) + ": the pending processor table (qtts_talker_set_row_processors) has " + std::to_string(w.size()) +
+                                      " rows, this call " + std::to_string(n));
+}
 // The pending warper table, taken by the call that consumes it (one-shot: whatever the call does next, the table is gone).  Empty: no
 // table was set.  A count other than the call's is refused before the call has changed anything.
 static std::vector<RowWarpers> take_warpers(qtts_talker* t, int n, const char* who) {
@@ -1472,6 +1538,11 @@ static std::vector<RowWarpers> take_warpers(qtts_talker* t, int n, const char* w
 }
 // a scalar call cannot consume a table: refused, and the table is dropped
 static void refuse_pending_warpers(qtts_talker* t, const char* who) {
+    if (t->proc_pending_set) {
+        t->proc_pending.clear(); t->proc_pending_set = false;
+        t->warp_pending.clear(); t->warp_pending_set = false;
+        throw Error(QTTS_ERR_ARG, std::string(who) + ": a processor table is pending (qtts_talker_set_row_processors); it belongs to a per-row table call");
+    }
     if (!t->warp_pending_set) return;
     t->warp_pending.clear();
     t->warp_pending_set = false;
@@ -1500,7 +1571,10 @@ static bool row_fast_talker(const SampleRow& o, int V) { return o.do_sample && o
 static bool row_fast_sub(const SampleRow& o, int Vc) { return o.sub_do_sample && o.sub_top_k > 0 && o.sub_top_k <= 64 && o.sub_top_k < Vc && Vc <= 4096; }
 static RowTable check_rows(qtts_talker* t, const qtts_row_sampling* rows, int n_rows, const char* who) {
     QTTS_REQUIRE(rows, QTTS_ERR_ARG, "null argument");
+    bool pset = false;
+    std::vector<RowProcessors> pr = take_processors(t, pset);      // (both tables are gone whatever this call does next)
     std::vector<RowWarpers> w = take_warpers(t, n_rows, who);
+    check_processor_count(pr, pset, n_rows, who);
     QTTS_REQUIRE(n_rows == t->B, QTTS_ERR_ARG, std::string(who) + ": n_rows (" + std::to_string(n_rows) + ") must equal the prefilled batch (" +
                                                    std::to_string(t->B) + ")");
     QTTS_REQUIRE(!t->tf.codes, QTTS_ERR_ARG, std::string(who) + ": teacher forcing takes scalar settings (qtts_talker_generate), not a per-row table");
@@ -1509,6 +1583,9 @@ static RowTable check_rows(qtts_talker* t, const qtts_row_sampling* rows, int n_
     r.tab.resize(n_rows);
     r.wtab.assign(n_rows, RowWarpers{});
     for (int b = 0; b < n_rows && !w.empty(); ++b) { r.wtab[b] = w[b]; r.warp = r.warp || warpers_on(w[b]); }
+    bool proc = false;
+    for (auto& e : pr) proc = proc || processors_on(e);
+    if (proc) { r.ptab.swap(pr); r.warp = true; }
     const int V = t->cfg.vocab_size, Vc = t->cfg.cp_vocab_size;
     for (int b = 0; b < n_rows; ++b) {
         const qtts_row_sampling& q = rows[b];
@@ -1534,8 +1611,13 @@ void qtts_talker::admit(int n_new, const int32_t* rows_host, const float* embeds
                         const qtts_row_sampling* settings, hipStream_t st) {
     const char* who = "stream_admit";
     auto& g = sg;
+    bool pset = false;
+    std::vector<RowProcessors> pnew = take_processors(this, pset);
     std::vector<RowWarpers> wnew = take_warpers(this, n_new, who);
+    check_processor_count(pnew, pset, n_new, who);
     if (wnew.empty()) wnew.assign(std::max(n_new, 0), RowWarpers{});
+    bool proc_new = false;
+    for (auto& e : pnew) proc_new = proc_new || processors_on(e);
     auto fail = [&](int code, int b, const std::string& what) { throw Error(code, std::string(who) + ": row " + std::to_string(b) + ": " + what); };
     QTTS_REQUIRE(n_new >= 1 && n_new <= B, QTTS_ERR_ARG, "stream_admit: 1 <= n_new <= the stream's rows");
     QTTS_REQUIRE(T >= 1 && Tt_ >= 1, QTTS_ERR_ARG, "stream_admit: T >= 1 and >= 1 trailing row");
@@ -1594,6 +1676,7 @@ void qtts_talker::admit(int n_new, const int32_t* rows_host, const float* embeds
     }
     bool warp_t = row_warp_t;                                // monotone like the classes above: the first warper of a stream re-captures once
     for (auto& e : wnew) warp_t = warp_t || warpers_on(e);
+    warp_t = warp_t || proc_new;
     if (warp_t != row_warp_t) {
         row_warp_t = warp_t;
         destroy_graph(); graph_nodes = 0;
@@ -1633,6 +1716,9 @@ void qtts_talker::admit(int n_new, const int32_t* rows_host, const float* embeds
         QTTS_CHECK_HIP(hipMemcpyAsync(n_pad_d.as<int>() + b, &npad_g[i], 4, hipMemcpyHostToDevice, st));
         QTTS_CHECK_HIP(hipMemcpyAsync(rows_d.as<SampleRow>() + b, &entries[i], sizeof(SampleRow), hipMemcpyHostToDevice, st));
         QTTS_CHECK_HIP(hipMemcpyAsync(warp_d.as<RowWarpers>() + b, &wnew[i], sizeof(RowWarpers), hipMemcpyHostToDevice, st));
+        // (the previous occupant's processors must not outlive it: a row admitted without any is cleared once the table has held some)
+        if (proc_new) QTTS_CHECK_HIP(hipMemcpyAsync(proc_d.as<RowProcessors>() + b, &pnew[i], sizeof(RowProcessors), hipMemcpyHostToDevice, st));
+        else if (proc_dirty) QTTS_CHECK_HIP(hipMemsetAsync(proc_d.as<RowProcessors>() + b, 0, sizeof(RowProcessors), st));
         QTTS_CHECK_HIP(hipMemcpyAsync(ss.unfinished + b, &one, 4, hipMemcpyHostToDevice, st));
         if (row_pos) QTTS_CHECK_HIP(hipMemcpyAsync(row_len_p + b, &T, 4, hipMemcpyHostToDevice, st));
     }
@@ -1650,11 +1736,12 @@ void qtts_talker::admit(int n_new, const int32_t* rows_host, const float* embeds
         p.tok_out = cur_tok.as<int>() + b; p.tok_stride = 1; p.unfinished = ss.unfinished + b; p.generated_out = generated.as<int>() + (size_t)b * gen_cap;
         p.max_new_tokens = g.max_new; p.done_in = ss.done;
         p.rows = rows_d.as<SampleRow>() + b; p.rows_sub = 0; p.rows_fast = row_fast_t;
-        if (row_warp_t) { SampleWarpParams pw{p, warp_d.as<RowWarpers>() + b}; launch_sample_warp(pw, st); }
+        if (row_warp_t) { SampleWarpParams pw{p, warp_d.as<RowWarpers>() + b, proc_d.as<RowProcessors>() + b}; launch_sample_warp(pw, st); }
         else launch_sample(p, st);
     }
     QTTS_CHECK_HIP(hipStreamSynchronize(st));      // (host buffers above must outlive the copies)
     for (int i = 0; i < n_new; ++i) { g.tab[rows_host[i]] = entries[i]; g.wtab[rows_host[i]] = wnew[i]; }
+    proc_dirty = proc_dirty || proc_new;
     if (row_pos) mirror_rows(st);
     g.done = 0;
     admit_calls += 1; admitted_rows += n_new;
@@ -1678,6 +1765,13 @@ static void upload_call_state(qtts_talker* t, const qtts_sampling& sp, const Row
     QTTS_CHECK_HIP(hipMemcpyAsync(t->seed_d.p, &seed, 8, hipMemcpyHostToDevice, st));
     if (rt) QTTS_CHECK_HIP(hipMemcpyAsync(t->rows_d.p, rt->tab.data(), rt->tab.size() * sizeof(SampleRow), hipMemcpyHostToDevice, st));
     if (rt) QTTS_CHECK_HIP(hipMemcpyAsync(t->warp_d.p, rt->wtab.data(), rt->wtab.size() * sizeof(RowWarpers), hipMemcpyHostToDevice, st));
+    if (rt && !rt->ptab.empty()) {
+        QTTS_CHECK_HIP(hipMemcpyAsync(t->proc_d.p, rt->ptab.data(), rt->ptab.size() * sizeof(RowProcessors), hipMemcpyHostToDevice, st));
+        t->proc_dirty = true;
+    } else if (rt && t->proc_dirty) {             // (a table call reads the processors only in class 3, but a later admission may bring that class)
+        QTTS_CHECK_HIP(hipMemsetAsync(t->proc_d.p, 0, (size_t)t->cfg.max_batch * sizeof(RowProcessors), st));
+        t->proc_dirty = false;
+    }
     QTTS_CHECK_HIP(hipStreamSynchronize(st));
     t->gen_cap = max_new;
     t->generated.ensure((size_t)t->B * max_new * 4);
@@ -2036,6 +2130,20 @@ int qtts_talker_set_row_warpers(qtts_talker* t, const qtts_row_warpers* rows_hos
     for (int b = 0; b < n_rows; ++b) w[b] = check_warpers(rows_host[b], b, "set_row_warpers");
     t->warp_pending.swap(w);
     t->warp_pending_set = true;
+    QTTS_API_END
+}
+
+int qtts_talker_set_row_processors(qtts_talker* t, const qtts_row_processors* rows_host, int32_t n_rows) {
+    QTTS_API_BEGIN
+    QTTS_REQUIRE(t, QTTS_ERR_ARG, "null handle");
+    t->proc_pending.clear();
+    t->proc_pending_set = false;
+    if (!rows_host || n_rows == 0) return 0;
+    QTTS_REQUIRE(n_rows >= 1 && n_rows <= t->cfg.max_batch, QTTS_ERR_ARG, "set_row_processors: 1 <= n_rows <= max_batch");
+    std::vector<RowProcessors> w(n_rows);
+    for (int b = 0; b < n_rows; ++b) w[b] = check_processors(rows_host[b], b, t->cfg.vocab_size, "set_row_processors");
+    t->proc_pending.swap(w);
+    t->proc_pending_set = true;
     QTTS_API_END
 }
 

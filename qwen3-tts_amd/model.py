@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from .config import TalkerConfig
-from .talker import _WARP_ARGS, TalkerEngine
+from .talker import _PROC_ARGS, _WARP_ARGS, TalkerEngine
 
 
 @dataclass
@@ -293,15 +293,18 @@ class Qwen3TTSForConditionalGeneration:
         and row it lands in, so a request's codes do not depend on what it was batched with.  With per-request knobs but ONE `seed` s,
         request i samples with s + i; with no seed, every request draws a fresh one: requests never share their random draws.
         `min_p`, `typical_p`, `epsilon_cutoff`, `eta_cutoff` and `no_repeat_ngram_size` (keywords; the talker's codebook-0 sampler,
-        `TalkerEngine.generate`) are per call or per request alike, and put the call on per-request seeds.  Other unknown keywords are
-        still ignored."""
+        `TalkerEngine.generate`) are per call or per request alike, and put the call on per-request seeds.  So are `sequence_bias`,
+        `bad_words_ids`, `min_length`, `forced_eos_token_id`, `exponential_decay_length_penalty` and `begin_suppress_tokens`: HF's own
+        form of a value is one value for the call, a list of one such value or None per request is per request
+        (`talker._split_row_processors`).  Other unknown keywords (`logits_processor`, `stopping_criteria`, `num_beams`,
+        `remove_invalid_values`, `renormalize_logits`, ...) are still ignored."""
         c = self.config
         embeds, mask, trailing, pad = self.assemble_prompts(input_ids, languages, speakers, instruct_ids,
                                                             non_streaming_mode, ref_ids, voice_clone_prompt)
         suppress = [i for i in range(c.vocab_size - 1024, c.vocab_size) if i != c.codec_eos_token_id]      # M:2059-2063
         codes_all, hidden_all = [], []
         mb = self.talker.max_batch
-        from .talker import _fresh_seed, _is_row_seq, _warp_table
+        from .talker import _fresh_seed, _is_row_seq, _proc_table, _split_row_processors, _warp_table
         n_req = embeds.shape[0]
         knobs = dict(max_new_tokens=max_new_tokens, do_sample=do_sample, top_k=top_k, top_p=top_p, temperature=temperature,
                      subtalker_dosample=subtalker_dosample, subtalker_top_k=subtalker_top_k, subtalker_top_p=subtalker_top_p,
@@ -312,6 +315,12 @@ class Qwen3TTSForConditionalGeneration:
         if _warp_table(n_req, **warped) is None:
             warped = {}
         knobs.update(warped)
+        # the processors likewise: as per-request lists (HF's forms of their values are lists themselves, so only the one rule can
+        # tell a shared value from a per-request list), and only when some request has one on
+        procs = _split_row_processors(n_req, **{k: kwargs.get(k) for k in _PROC_ARGS})
+        ptab, floors = _proc_table(n_req, c.vocab_size, eos_token_id if eos_token_id is not None else c.codec_eos_token_id, **procs)
+        if ptab is None and not any(floors):
+            procs = {}
         seed = kwargs.get("seed")
         for k, v in list(knobs.items()) + [("seed", seed)]:
             if _is_row_seq(v) and len(v) != n_req:
@@ -329,10 +338,11 @@ class Qwen3TTSForConditionalGeneration:
             # "continuous": on one stream with per-row positions)
             out = self.talker.generate(embeds, mask, trailing, pad, min_new_tokens=2,
                                        eos_token_id=eos_token_id if eos_token_id is not None else c.codec_eos_token_id,
-                                       suppress_tokens=suppress, seed=seed, schedule=schedule, **knobs)
+                                       suppress_tokens=suppress, seed=seed, schedule=schedule, **knobs, **procs)
             return self._trim_at_eos(out, codes_all, hidden_all)
         # (a warper runs on the per-row table, whose Philox counter has no row term: every request then needs a seed of its own)
-        per_request = any(_is_row_seq(v) for v in knobs.values()) or _is_row_seq(seed) or bool(warped)
+        per_request = any(_is_row_seq(v) for v in knobs.values()) or _is_row_seq(seed) or bool(warped) or bool(procs)
+        knobs.update(procs)
         if per_request:
             seeds = list(seed) if _is_row_seq(seed) else ([int(seed) + i for i in range(n_req)] if seed is not None else [None] * n_req)
         else:
@@ -394,7 +404,7 @@ class Qwen3TTSForConditionalGeneration:
                                                   subtalker_temperature=subtalker_temperature, eos_token_id=eos,
                                                   repetition_penalty=repetition_penalty, suppress_tokens=suppress,
                                                   seed=kwargs.get("seed"), schedule=schedule,
-                                                  **{k: kwargs[k] for k in _WARP_ARGS if kwargs.get(k) is not None}):
+                                                  **{k: kwargs[k] for k in _WARP_ARGS + _PROC_ARGS if kwargs.get(k) is not None}):
             if schedule != "waves":
                 yield packet
                 continue
@@ -562,6 +572,11 @@ class Qwen3TTSModel:
                 merged[k] = [default if x is None else x for x in v]
             elif v is not None or default is not None:
                 merged[k] = v if v is not None else default
+        # ... and its remaining logits processors: the user's value as it is (their values are lists themselves: which lists are per
+        # request is `talker._split_row_processors`' one rule), else generate_config.json's
+        for k in _PROC_ARGS:
+            if kwargs.get(k) is None and self.generate_defaults.get(k) is not None:
+                merged[k] = self.generate_defaults[k]
         return merged
 
     def _unsupported(self, what: str):
@@ -870,12 +885,14 @@ class Qwen3TTSModel:
         as `Qwen3TTSForConditionalGeneration.generate` runs them (per-request sequences sliced per wave; one seed s: wave w samples with
         s + w, or request i with s + i once any knob is per request).  `stream_wave(slice, **kwargs)` is `generate_stream` on one wave;
         request i of a wave occupies row i."""
-        from .talker import RefillPacket, RefillRow, _is_row_seq, _warp_table
+        from .talker import RefillPacket, RefillRow, _is_row_seq, _split_row_processors, _warp_table
         mb = self.model.talker.max_batch
         seed = gen_kwargs.get("seed")
         knobs = {k: v for k, v in gen_kwargs.items() if k != "seed"}
         warped = {k: knobs[k] for k in _WARP_ARGS if knobs.get(k) is not None}
-        per_request = any(_is_row_seq(v) for v in knobs.values()) or _is_row_seq(seed) or _warp_table(n_req, **warped) is not None
+        procs = _split_row_processors(n_req, **{k: knobs.get(k) for k in _PROC_ARGS})      # (per-request lists: sliced like the knobs)
+        knobs.update(procs)
+        per_request = (any(_is_row_seq(v) for v in knobs.values()) or _is_row_seq(seed) or _warp_table(n_req, **warped) is not None)
         if per_request and not _is_row_seq(seed):
             seed = [int(seed) + i for i in range(n_req)] if seed is not None else None
         for b0 in range(0, n_req, mb):

@@ -41,7 +41,7 @@ class TalkerGenerateOutput:
 @dataclass
 class _Call:
     """A generation call as `TalkerEngine._prepare` hands it to `generate`, `generate_stream` and the refill schedules: checked, on the
-    device, settings resolved.  Exactly one of `rows` (the per-row table; `warp` may come with it) and `sp` (the scalar path) is set."""
+    device, settings resolved.  Exactly one of `rows` (the per-row table; `warp` and `proc` may come with it) and `sp` (the scalar path) is set."""
     B: int
     T: int
     n_pad: List[int]
@@ -55,6 +55,7 @@ class _Call:
     sup_c: Any
     rows: Any                  # `_lib.RowSamplingC` x B, or None
     warp: Any                  # `_lib.RowWarpersC` x B, or None
+    proc: Any                  # `_lib.RowProcessorsC` x B, or None
     sp: Any                    # `_lib.SamplingC`, or None
     max_new_tokens: int        # clamped to the KV capacity; on the table the largest limit (buffers are sized by it)
     min_new_tokens: Any        # as given (the scalar path passes it on; the table holds its own)
@@ -171,6 +172,156 @@ def _warp_table(B: int, **kw):
         e.min_p, e.typical_p, e.epsilon_cutoff, e.eta_cutoff, e.no_repeat_ngram_size = vals
         on = on or any(vals)
     return rows if on else None
+
+
+# the talker's remaining HF logits processors (include/qtts.h `qtts_row_processors`; `min_length` is folded into the row's EOS floor)
+_PROC_ARGS = ("sequence_bias", "bad_words_ids", "min_length", "forced_eos_token_id", "exponential_decay_length_penalty",
+              "begin_suppress_tokens")
+
+
+def _is_num(v) -> bool:
+    return v is not None and not isinstance(v, (list, tuple, dict, str))
+
+
+def _is_ids(v) -> bool:
+    return isinstance(v, (list, tuple)) and all(_is_num(x) for x in v)
+
+
+# HF's own form of each value: such a value is ONE value for the call
+_PROC_IS_VALUE = {
+    "sequence_bias": lambda v: isinstance(v, dict) or (isinstance(v, list) and all(
+        isinstance(x, (list, tuple)) and len(x) == 2 and _is_ids(x[0]) and _is_num(x[1]) for x in v)),
+    "bad_words_ids": lambda v: isinstance(v, list) and all(_is_ids(x) for x in v),
+    "min_length": _is_num,
+    "forced_eos_token_id": _is_num,
+    "exponential_decay_length_penalty": lambda v: isinstance(v, (list, tuple)) and len(v) == 2 and _is_num(v[0]) and _is_num(v[1]),
+    "begin_suppress_tokens": _is_ids,
+}
+
+
+def _split_row_processors(B: int, **kw) -> Dict[str, list]:
+    """Which of the `_PROC_ARGS` values are shared and which are per request -- the one rule, used by every entry: HF's own form of a
+    value is one value for the call; a list of length B whose items are each None (off for that request) or such a value is per
+    request; a list of such items of any other length raises, naming the argument.  (`forced_eos_token_id`: a list is therefore always
+    per request.)  Anything else is passed on as one value, for `_resolve_row_processors` to refuse in HF's wording.  Returns
+    {name: list of B values}, for the names that are given."""
+    out = {}
+    for k in _PROC_ARGS:
+        v = kw.get(k)
+        if v is None:
+            continue
+        if not _PROC_IS_VALUE[k](v) and isinstance(v, (list, tuple)) and all(x is None or _PROC_IS_VALUE[k](x) for x in v):
+            if len(v) != B:
+                raise ValueError(f"`{k}` has {len(v)} entries for a batch of {B} requests")
+            out[k] = list(v)
+        else:
+            out[k] = [v] * B
+    return out
+
+
+def _sequence_bias_dict(sequence_bias) -> dict:
+    """SequenceBiasLogitsProcessor's `_validate_arguments` and `_convert_list_arguments_into_dict`, in HF's wording."""
+    import numbers
+    sb = sequence_bias
+    is_id = lambda t: isinstance(t, numbers.Integral) and not isinstance(t, bool)
+    if (not isinstance(sb, dict) and not isinstance(sb, list)) or len(sb) == 0:
+        raise ValueError(f"`sequence_bias` has to be a non-empty dictionary, or non-empty list of lists but is {sb}.")
+    if isinstance(sb, dict):
+        if any(not isinstance(ids, tuple) for ids in sb):
+            raise ValueError(f"`sequence_bias` has to be a dict with tuples as keys, but is {sb}.")
+        if any(any((not is_id(t) or t < 0) for t in ids) or len(ids) == 0 for ids in sb):
+            raise ValueError(f"Each key in `sequence_bias` has to be a non-empty tuple of positive integers, but is {sb}.")
+        if any(not isinstance(b, float) for b in sb.values()):
+            raise ValueError(f"`sequence_bias` has to be a dict with floats as values, but is {sb}.")
+        return dict(sb)
+    ok = lambda s: (isinstance(s, (list, tuple)) and len(s) == 2 and isinstance(s[0], list) and len(s[0]) > 0
+                    and all(is_id(t) and t > 0 for t in s[0]) and isinstance(s[1], float))
+    if any(not ok(s) for s in sb):
+        raise ValueError(f"Each element in `sequence_bias` has to be a non-empty list of lists of positive integers and float, but is {sb}.")
+    return {tuple(s[0]): s[1] for s in sb}
+
+
+def _resolve_row_processors(V: int, eos: int, sequence_bias=None, bad_words_ids=None, min_length=None, forced_eos_token_id=None,
+                            exponential_decay_length_penalty=None, begin_suppress_tokens=None):
+    """One request's remaining HF logits processors as the engine takes them: (records [(kind, ids, bias)], flags, decay_start,
+    decay_factor, min_length).  Gating is transformers' `_get_logits_processor` (None is off; `min_length` acts for > 0); values HF's
+    constructors refuse raise with HF's wording, a token id >= V as its first call does.  A single-token bad word equal to `eos` is
+    dropped, as HF drops it.  Only the call's own eos can be forced."""
+    import numbers
+    is_id = lambda t: isinstance(t, numbers.Integral) and not isinstance(t, bool)
+    records = []
+
+    def in_vocab(seqs):
+        bad = [int(t) for ids in seqs for t in ids if t >= V]
+        if bad:
+            raise ValueError(f"The model vocabulary size is {V}, but the following tokens were being biased: {bad}")
+
+    if sequence_bias is not None:
+        sb = _sequence_bias_dict(sequence_bias)
+        in_vocab(sb)
+        records += [(_lib.PROC_KIND_BIAS, [int(t) for t in ids], float(b)) for ids, b in sb.items()]
+    if bad_words_ids is not None:
+        bw = bad_words_ids
+        if not isinstance(bw, list) or len(bw) == 0:
+            raise ValueError(f"`bad_words_ids` has to be a non-empty list, but is {bw}.")
+        if any(not isinstance(ids, list) for ids in bw):
+            raise ValueError(f"`bad_words_ids` has to be a list of lists, but is {bw}.")
+        if any(any((not is_id(t) or t < 0) for t in ids) for ids in bw):
+            raise ValueError(f"Each list in `bad_words_ids` has to be a list of positive integers, but is {bw}.")
+        banned = _sequence_bias_dict({tuple(ids): float("-inf") for ids in bw if list(ids) != [eos]})
+        in_vocab(banned)
+        records += [(_lib.PROC_KIND_BAN, [int(t) for t in ids], 0.0) for ids in banned]
+    floor = 0
+    if min_length is not None:
+        if not is_id(min_length) or min_length < 0:
+            raise ValueError(f"`min_length` has to be a non-negative integer, but is {min_length}")
+        floor = int(min_length)
+    flags, start, factor = 0, 0, 0.0
+    if forced_eos_token_id is not None:
+        if not is_id(forced_eos_token_id) or int(forced_eos_token_id) != int(eos):
+            raise ValueError(f"`forced_eos_token_id` can only force the call's own eos_token_id ({eos}), one id per request (a list is "
+                             f"read as one value per request, not as HF's list of ids), but is {forced_eos_token_id}")
+        flags |= _lib.PROC_FORCED_EOS
+    if exponential_decay_length_penalty is not None:
+        d = exponential_decay_length_penalty
+        if not (isinstance(d, (list, tuple)) and len(d) == 2 and is_id(d[0]) and isinstance(d[1], numbers.Real) and float(d[1]) > 0.0
+                and float(d[1]) != float("inf")):
+            raise ValueError(f"`exponential_decay_length_penalty` has to be a (start_index, decay_factor) pair of an integer and a "
+                             f"positive float, but is {d}")
+        flags |= _lib.PROC_DECAY
+        start, factor = int(d[0]), float(d[1])
+    if begin_suppress_tokens is not None and len(begin_suppress_tokens) > 0:
+        ids = list(begin_suppress_tokens)
+        if any(not is_id(t) or t < 0 or t >= V for t in ids):
+            raise ValueError(f"`begin_suppress_tokens` has to be a list of token ids in [0, {V}), but is {ids}")
+        records.append((_lib.PROC_KIND_BEGIN, [int(t) for t in ids], 0.0))
+    return records, flags, start, factor, floor
+
+
+def _proc_table(B: int, V: int, eos: int, **kw):
+    """The processor table of a call (`_lib.RowProcessorsC` x B) from the `_PROC_ARGS` (`_split_row_processors` says which values are
+    per request), or None when no request has a device control on; and every request's `min_length`.  A request beyond the table's
+    capacity per row raises ValueError, as the engine would refuse it (QTTS_ERR_LIMIT)."""
+    cols = _split_row_processors(B, **kw)
+    if not cols:
+        return None, [0] * B
+    rows = (_lib.RowProcessorsC * B)()
+    on, floors = False, []
+    for b in range(B):
+        records, flags, start, factor, floor = _resolve_row_processors(V, eos, **{k: v[b] for k, v in cols.items()})
+        floors.append(floor)
+        n_tok = sum(len(ids) for _, ids, _ in records)
+        if len(records) > _lib.PROC_MAX_RECORDS or n_tok > _lib.PROC_MAX_TOKENS:
+            raise ValueError(f"request {b}: {len(records)} sequences with {n_tok} tokens exceed the engine's capacity per request "
+                             f"({_lib.PROC_MAX_RECORDS} sequences, {_lib.PROC_MAX_TOKENS} tokens)")
+        words = []
+        for kind, ids, bias in records:
+            words += [kind, len(ids), C.c_int32.from_buffer_copy(C.c_float(bias)).value] + ids
+        e = rows[b]
+        e.decay_factor, e.decay_start, e.flags, e.n_records, e.n_words = factor, start, flags, len(records), len(words)
+        e.records[:len(words)] = words
+        on = on or bool(flags or records)
+    return (rows if on else None), floors
 
 
 def _is_row_seq(v) -> bool:
@@ -420,7 +571,9 @@ class TalkerEngine:
                  subtalker_top_k: Optional[int] = 50, subtalker_top_p: Optional[float] = 1.0,
                  subtalker_temperature: Optional[float] = 0.9, eos_token_id: Optional[int] = None,
                  repetition_penalty: float = 1.05, suppress_tokens: Optional[List[int]] = None, seed: Optional[int] = None,
-                 min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None, no_repeat_ngram_size=None, **unused) -> _Call:
+                 min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None, no_repeat_ngram_size=None,
+                 sequence_bias=None, bad_words_ids=None, min_length=None, forced_eos_token_id=None,
+                 exponential_decay_length_penalty=None, begin_suppress_tokens=None, **unused) -> _Call:
         """The arguments of a generation call (`generate`, `generate_stream` and the refill schedules take them alike), checked and
         made ready: shapes, the left-padded mask, the per-row and warper tables or the scalar settings, eos and the suppress list, the
         three tensors on the device.  `queue_mode` (the refill schedules): the rows are a queue of requests, not a batch -- any number
@@ -436,8 +589,19 @@ class TalkerEngine:
         `min_p`, `typical_p`, `epsilon_cutoff`, `eta_cutoff` and `no_repeat_ngram_size` (HF generate's remaining sampling controls, for
         the codebook-0 sampler; gating and errors as in transformers, `_resolve_row_warpers`) are one value or a sequence of B as well.
         Any of them that is on puts the call on the per-row table (scalars are broadcast; ONE integer seed s gives request b the seed
-        s + b) and the talker's sampler becomes `sample_warp_kernel` (`sampler_class()` reports 3).  Any OTHER keyword this signature
-        does not name is still swallowed."""
+        s + b) and the talker's sampler becomes `sample_warp_kernel` (`sampler_class()` reports 3).
+
+        `sequence_bias`, `bad_words_ids`, `min_length`, `forced_eos_token_id`, `exponential_decay_length_penalty` and
+        `begin_suppress_tokens` (HF generate's remaining logits processors, for the codebook-0 sampler; chain order, gating and errors
+        as in transformers: `_resolve_row_processors`, include/qtts.h `qtts_row_processors`) each take HF's own form of the value for
+        the whole call or a list with one such value -- or None, off -- per request (`_split_row_processors`).  A request's `cur_len`
+        is its own generated count, under every schedule.  `min_length` is folded into the request's EOS floor,
+        max(min_length, min_new_tokens), and needs no device work; any of the others that is on puts the call on the per-row table
+        and on `sample_warp_kernel` like a warper.  `forced_eos_token_id` can only be the call's own eos: at the request's token index
+        limit - 1 every score but EOS is removed, where limit is the request's EFFECTIVE `max_new_tokens` -- after the clamp to the
+        room `max_seq` leaves (`_clamp_new_tokens`); it comes behind the EOS floor in the chain and wins over it.
+        `exponential_decay_length_penalty=(start, factor)`: the power factor ** (cur_len - start) is evaluated in double on the
+        device, the rest in fp32, as HF does.  Any OTHER keyword this signature does not name is still swallowed."""
         c, dev = self.config, self.device
         if inputs_embeds.dim() != 3 or inputs_embeds.shape[-1] != c.hidden_size:
             raise ValueError(f"inputs_embeds must be (B, T, {c.hidden_size})")
@@ -459,10 +623,21 @@ class TalkerEngine:
         # (a request keeps its entries of both tables through queueing, admission and restart)
         warp = _warp_table(B, min_p=min_p, typical_p=typical_p, epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff,
                            no_repeat_ngram_size=no_repeat_ngram_size)
+        eos = c.codec_eos_token_id if eos_token_id is None else int(eos_token_id)
+        proc, floors = _proc_table(B, c.vocab_size, eos, sequence_bias=sequence_bias, bad_words_ids=bad_words_ids, min_length=min_length,
+                                   forced_eos_token_id=forced_eos_token_id,
+                                   exponential_decay_length_penalty=exponential_decay_length_penalty,
+                                   begin_suppress_tokens=begin_suppress_tokens)
+        if any(floors):          # MinLength and MinNewTokensLength block the same token: one floor per request
+            mins = [_scalar(x) for x in min_new_tokens] if _is_row_seq(min_new_tokens) else [min_new_tokens] * B
+            if len(mins) != B:
+                raise ValueError(f"`min_new_tokens` has {len(mins)} entries for a batch of {B} requests")
+            mins = [max(int(m) if m is not None else 0, f) for m, f in zip(mins, floors)]
+            min_new_tokens = mins if _is_row_seq(min_new_tokens) or len(set(mins)) > 1 else mins[0]
         knobs = dict(do_sample=do_sample, top_k=top_k, top_p=top_p, temperature=temperature, repetition_penalty=repetition_penalty,
                      subtalker_dosample=subtalker_dosample, subtalker_top_k=subtalker_top_k, subtalker_top_p=subtalker_top_p,
                      subtalker_temperature=subtalker_temperature, max_new_tokens=max_new_tokens, min_new_tokens=min_new_tokens, seed=seed)
-        table = self._row_table(B, lens if queue_mode else T, force=queue_mode or warp is not None, **knobs)
+        table = self._row_table(B, lens if queue_mode else T, force=queue_mode or warp is not None or proc is not None, **knobs)
         rows = sp = None
         if table is not None:
             rows, max_new_tokens = table                  # buffers are sized by the largest limit
@@ -479,9 +654,9 @@ class TalkerEngine:
         if pad.numel() != H:
             raise ValueError("tts_pad_embed must have H elements")
         return _Call(B=B, T=T, n_pad=n_pad, lens=lens, emb=emb, trail=trail, pad=pad,
-                     eos=c.codec_eos_token_id if eos_token_id is None else int(eos_token_id), suppress=suppress,
+                     eos=eos, suppress=suppress,
                      npad_c=(C.c_int32 * B)(*n_pad), sup_c=(C.c_int32 * max(1, len(suppress)))(*[int(x) for x in suppress]),
-                     rows=rows, warp=warp, sp=sp, max_new_tokens=max_new_tokens, min_new_tokens=min_new_tokens)
+                     rows=rows, warp=warp, proc=proc, sp=sp, max_new_tokens=max_new_tokens, min_new_tokens=min_new_tokens)
 
     def _generate_once(self, inputs_embeds: torch.Tensor, *args, output_hidden_states: bool = True,
                        teacher_codes: Optional[torch.Tensor] = None, logit_steps: Optional[List[int]] = None, **kw) -> TalkerGenerateOutput:
@@ -538,6 +713,8 @@ class TalkerEngine:
                 if p.rows is not None:
                     if p.warp is not None:
                         _lib.check(self._lib.qtts_talker_set_row_warpers(self._h, p.warp, B))
+                    if p.proc is not None:
+                        _lib.check(self._lib.qtts_talker_set_row_processors(self._h, p.proc, B))
                     _lib.check(self._lib.qtts_talker_generate_rows(self._h, p.rows, B, p.eos, p.sup_c, len(suppress_tokens), *out_c))
                 else:
                     _lib.check(self._lib.qtts_talker_generate(self._h, C.byref(p.sp), int(max_new_tokens), int(p.min_new_tokens), p.eos,
@@ -558,7 +735,8 @@ class TalkerEngine:
                         subtalker_temperature: Optional[float] = 0.9, eos_token_id: Optional[int] = None,
                         repetition_penalty: float = 1.05, suppress_tokens: Optional[List[int]] = None,
                         seed: Optional[int] = None, schedule: str = "waves", min_p=None, typical_p=None, epsilon_cutoff=None,
-                        eta_cutoff=None, no_repeat_ngram_size=None, **unused):
+                        eta_cutoff=None, no_repeat_ngram_size=None, sequence_bias=None, bad_words_ids=None, min_length=None,
+                        forced_eos_token_id=None, exponential_decay_length_penalty=None, begin_suppress_tokens=None, **unused):
         """Streaming OUTPUT (include/qtts.h `qtts_talker_stream_*`): a generator that yields `codes[:, f0:f1]` (B, k, G)
         int64 device tensors, k <= packet_frames, as the frames are produced; same arguments (per-request sequences included) and the
         same frames as `generate`.  Closing the generator early abandons the request.  Holds the engine lock while active.
@@ -571,7 +749,9 @@ class TalkerEngine:
                   temperature=temperature, subtalker_dosample=subtalker_dosample, subtalker_top_k=subtalker_top_k,
                   subtalker_top_p=subtalker_top_p, subtalker_temperature=subtalker_temperature, eos_token_id=eos_token_id,
                   repetition_penalty=repetition_penalty, suppress_tokens=suppress_tokens, seed=seed, min_p=min_p, typical_p=typical_p,
-                  epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff, no_repeat_ngram_size=no_repeat_ngram_size)
+                  epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff, no_repeat_ngram_size=no_repeat_ngram_size,
+                  sequence_bias=sequence_bias, bad_words_ids=bad_words_ids, min_length=min_length, forced_eos_token_id=forced_eos_token_id,
+                  exponential_decay_length_penalty=exponential_decay_length_penalty, begin_suppress_tokens=begin_suppress_tokens)
         if schedule in ("refill", "continuous"):
             yield from self._refill_stream(inputs_embeds, attention_mask, trailing_text_hidden, tts_pad_embed, packet_frames=packet_frames,
                                            row_positions=schedule == "continuous", **kw)
@@ -593,6 +773,8 @@ class TalkerEngine:
                 if p.rows is not None:
                     if p.warp is not None:
                         _lib.check(self._lib.qtts_talker_set_row_warpers(self._h, p.warp, B))
+                    if p.proc is not None:
+                        _lib.check(self._lib.qtts_talker_set_row_processors(self._h, p.proc, B))
                     _lib.check(self._lib.qtts_talker_stream_begin_rows(self._h, p.rows, B, p.eos, p.sup_c, n_sup,
                                                                        C.c_void_p(codes.data_ptr()), None, self._s()))
                 else:
@@ -616,13 +798,14 @@ class TalkerEngine:
     @_lib.locked
     def stream_open(self, inputs_embeds: torch.Tensor, n_pad: List[int], trailing_text_hidden: torch.Tensor, tts_pad_embed: torch.Tensor,
                     rows, max_row_tokens: int, eos_token_id: int, suppress_tokens: List[int], output_hidden_states: bool = False,
-                    row_positions: bool = False, warpers=None):
+                    row_positions: bool = False, warpers=None, processors=None):
         """Prefill + `qtts_talker_stream_begin_admitting`: `rows` is a `_lib.RowSamplingC` array with one entry per row of
         `inputs_embeds` (B, T, H; row b left-padded by n_pad[b]).  Returns (codes (B, max_row_tokens - 1, G), hidden or None): the
         blocks the stream fills, ONE occupant per row at a time -- copy a finished row out before `stream_admit` re-uses it.
         `row_positions=True` opens the stream with `qtts_talker_stream_begin_admitting_rows`: every row carries its own KV length, an
         admitted prompt restarts its row at its own length, and `stream_row_lens()` reads the lengths back.  `warpers`: a
-        `_lib.RowWarpersC` array with one entry per row (`qtts_talker_set_row_warpers`), or None."""
+        `_lib.RowWarpersC` array with one entry per row (`qtts_talker_set_row_warpers`), or None; `processors`: a `_lib.RowProcessorsC`
+        array likewise (`qtts_talker_set_row_processors`)."""
         c, dev = self.config, self.device
         B, T, H = inputs_embeds.shape
         if B > self.max_batch:
@@ -643,6 +826,8 @@ class TalkerEngine:
             begin = self._lib.qtts_talker_stream_begin_admitting_rows if row_positions else self._lib.qtts_talker_stream_begin_admitting
             if warpers is not None:
                 _lib.check(self._lib.qtts_talker_set_row_warpers(self._h, warpers, B))
+            if processors is not None:
+                _lib.check(self._lib.qtts_talker_set_row_processors(self._h, processors, B))
             _lib.check(begin(
                 self._h, rows, B, int(max_row_tokens), int(eos_token_id), sup_c, len(suppress_tokens), C.c_void_p(codes.data_ptr()),
                 C.c_void_p(hidden.data_ptr()) if hidden is not None else None, self._s()))
@@ -651,9 +836,9 @@ class TalkerEngine:
 
     @_lib.locked
     def stream_admit(self, row_ids: List[int], inputs_embeds: torch.Tensor, n_pad: List[int], trailing_text_hidden: torch.Tensor, rows,
-                     warpers=None):
+                     warpers=None, processors=None):
         """`qtts_talker_stream_admit`: request i of the group (inputs_embeds (n, T', H) left-padded by n_pad[i], trailing (n, Tt', H),
-        settings rows[i], warpers[i] of a `_lib.RowWarpersC` array if given) takes the finished row row_ids[i] of the open stream."""
+        settings rows[i], warpers[i] of a `_lib.RowWarpersC` array and processors[i] of a `_lib.RowProcessorsC` array if given) takes the finished row row_ids[i] of the open stream."""
         dev = self.device
         n, T, H = inputs_embeds.shape
         emb = inputs_embeds.to(dev, torch.float32).contiguous()
@@ -664,6 +849,8 @@ class TalkerEngine:
         with torch.cuda.device(dev), torch.cuda.stream(self._stream):
             if warpers is not None:
                 _lib.check(self._lib.qtts_talker_set_row_warpers(self._h, warpers, n))
+            if processors is not None:
+                _lib.check(self._lib.qtts_talker_set_row_processors(self._h, processors, n))
             _lib.check(self._lib.qtts_talker_stream_admit(self._h, n, ids_c, C.c_void_p(emb.data_ptr()), T, npad_c,
                                                           C.c_void_p(trail.data_ptr()), trail.shape[1], rows, self._s()))
 
@@ -781,15 +968,16 @@ class TalkerEngine:
             for k in range(len(idx) - spare, len(idx)):
                 tab[k].max_new_tokens, tab[k].min_new_tokens = 1, 0
             wtab = (_lib.RowWarpersC * len(idx))(*[p.warp[i] for i in idx]) if p.warp is not None else None
-            return p.emb[idx][:, p.T - Tg:], [Tg - p.lens[i] for i in idx], p.trail[idx], tab, wtab
+            ptab = (_lib.RowProcessorsC * len(idx))(*[p.proc[i] for i in idx]) if p.proc is not None else None
+            return p.emb[idx][:, p.T - Tg:], [Tg - p.lens[i] for i in idx], p.trail[idx], tab, wtab, ptab
 
         with self._lock:
             caps0 = self.stats()["graph_captures"]
             try:
                 while pol.queue:
-                    e, npd, tr, tab, wtab = group(*pol.open_stream())
+                    e, npd, tr, tab, wtab, ptab = group(*pol.open_stream())
                     codes, hidden = self.stream_open(e, npd, tr, p.pad, tab, p.max_new_tokens, p.eos, p.suppress, output_hidden_states,
-                                                     row_positions, warpers=wtab)
+                                                     row_positions, warpers=wtab, processors=ptab)
                     try:
                         while pol.active:
                             # (pooled: the engine's counts are read again after every eviction)
@@ -802,8 +990,8 @@ class TalkerEngine:
                                                           hidden=hidden[r.row, r.k0:r.k1].clone() if hidden is not None else None)
                                                 for r in pol.reports(unfinished, frames)])
                             for row_ids, grp in pol.admissions(kv_len, self.stream_kv()[1] if pol.tight else None):
-                                e, npd, tr, tab, wtab = group(grp)
-                                self.stream_admit(row_ids, e, npd, tr, tab, warpers=wtab)
+                                e, npd, tr, tab, wtab, ptab = group(grp)
+                                self.stream_admit(row_ids, e, npd, tr, tab, warpers=wtab, processors=ptab)
                     finally:
                         pol.stream_closed(self.stats(), self.stream_close())
             finally:
