@@ -59,7 +59,8 @@ const char* qtts_last_error(void);
  * qtts_talker_sampler_class -- a new struct and two entry points, no existing signature or struct changed; still 15:
  * + qtts_codec_stream_prime_rows, qtts_codec_stream_prime_tail -- two entry points added, no signature and no struct changed; a binding
  * that needs them finds out by looking the symbols up; still 15: + qtts_row_processors, qtts_talker_set_row_processors -- a new
- * struct and one entry point, no existing signature or struct changed). */
+ * struct and one entry point, no existing signature or struct changed; still 15: + qtts_speaker_embed_ragged -- one entry point
+ * added, no signature and no struct changed). */
 #define QTTS_ABI_VERSION 15
 int qtts_abi_version(void);
 
@@ -292,6 +293,17 @@ int qtts_speaker_mel_frames(qtts_speaker* s, int64_t samples, int64_t* frames);
  * (B, mel_frames, mel_dim) (the log-mel features, for tests). */
 int qtts_speaker_embed(qtts_speaker* s, const float* wav_dev, int32_t B, int32_t samples, float* emb_dev, float* mels_dev,
                        void* stream);
+/* qtts_speaker_embed for B clips of DIFFERENT lengths in one launch sequence.  Packed layout, nothing padded to the longest clip:
+ * wav_dev float device holds clip b's samples_host[b] samples at offset sum(samples_host[0..b)); samples_host int32 (B) is HOST memory,
+ * read before the call returns.  emb_dev float (B, enc_dim): row b is what qtts_speaker_embed gives for clip b alone (same arithmetic,
+ * stage for stage; reflect paddings, time means / deviations and the attention softmax run over the clip's own frames).  mels_dev
+ * optional float (sum_b mel_frames(samples_host[b]), mel_dim): the clips' log-mel frames one after the other.
+ * Refused before anything is launched or written, the message naming the clip: B outside 1..max_batch or a samples_host[b] outside
+ * 1..max_samples (QTTS_ERR_LIMIT); a clip shorter than one STFT window, or with no more mel frames than the widest reflect padding of
+ * the configured TDNN layers (QTTS_ERR_ARG) -- with the released kernel sizes and dilations the shortest clip is 1280 samples
+ * (5 frames), as in the reference. */
+int qtts_speaker_embed_ragged(qtts_speaker* s, const float* wav_dev, int32_t B, const int32_t* samples_host, float* emb_dev,
+                              float* mels_dev, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Talker + code predictor: the autoregressive speech-token decoder.

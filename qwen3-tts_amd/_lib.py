@@ -124,7 +124,7 @@ SYMBOLS = ["qtts_last_error", "qtts_abi_version", "qtts_set_option", "qtts_get_o
            "qtts_encoder_create", "qtts_encoder_destroy", "qtts_encoder_bind", "qtts_encoder_finalize", "qtts_encoder_frames",
            "qtts_encoder_encode",
            "qtts_speaker_create", "qtts_speaker_destroy", "qtts_speaker_bind", "qtts_speaker_finalize", "qtts_speaker_mel_frames",
-           "qtts_speaker_embed",
+           "qtts_speaker_embed", "qtts_speaker_embed_ragged",
            "qtts_talker_create", "qtts_talker_destroy", "qtts_talker_bind", "qtts_talker_finalize",
            "qtts_talker_text_projection", "qtts_talker_text_embed", "qtts_talker_assemble_rows", "qtts_talker_prefill",
            "qtts_talker_generate", "qtts_talker_stream_begin", "qtts_talker_stream_step", "qtts_talker_stream_end",
@@ -211,6 +211,7 @@ def load_library():
     lib.qtts_speaker_finalize.argtypes = [vp]
     lib.qtts_speaker_mel_frames.argtypes = [vp, C.c_int64, i64p]
     lib.qtts_speaker_embed.argtypes = [vp, f32p, i32, i32, f32p, f32p, vp]
+    lib.qtts_speaker_embed_ragged.argtypes = [vp, f32p, i32, C.POINTER(C.c_int32), f32p, f32p, vp]
     lib.qtts_talker_create.argtypes = [C.POINTER(TalkerConfigC), C.POINTER(vp)]
     lib.qtts_talker_destroy.argtypes = [vp]
     lib.qtts_talker_destroy.restype = None

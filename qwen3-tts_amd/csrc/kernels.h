@@ -197,6 +197,28 @@ void launch_scale_add_rows(const float* h, int ldh, const float* gate, const flo
 void launch_concat_stats(const float* x, int ldx, const float* mean, const float* sd, int T, int C, float* out, int B, hipStream_t st);
 // softmax over t for every (b, c), in place
 void launch_softmax_time(float* a, int T, int C, int B, hipStream_t st);
+// ---- ragged forms: clips of different lengths packed row after row (qtts_speaker_embed_ragged).  seg[b] (device, B entries) gives
+// clip b's first input row, first output row and its length at this stage; max_rows / max_len = the longest clip's (the row grid).
+struct RagSeg { int in_off, out_off, len; };
+// out[out_off + r][j] = wav[in_off + reflect(r*hop + j - pad)] for r < (len + 2*pad) / hop; in_off / len in samples
+void launch_reflect_rows_1d_rag(const float* wav, const RagSeg* seg, int pad, int max_rows, int hop, float* out, int B, hipStream_t st);
+// dst[out_off + i][c] = src1[in_off + reflect(i - p)][c] (+ src2[...]) for i in [0, len + 2p)
+void launch_reflect_pad_add_rows_rag(const float* src1, int ld1, const float* src2, int ld2, const RagSeg* seg, int max_len, int p, int C,
+                                     float* dst, int B, hipStream_t st);
+// dst[(out_off + t)*ldd + c] = act(src[(in_off + skip + t)*lds + c]) for t < len, c < C
+void launch_copy_act_rows_rag(const float* src, int lds, const RagSeg* seg, int max_len, int skip, int C, int act, float* dst, int ldd,
+                              int B, hipStream_t st);
+// launch_col_stats over rows in_off .. in_off + len of x (and att) for clip b; w = 1/len when att == null
+void launch_col_stats_rag(const float* x, int ldx, const float* att, const RagSeg* seg, int C, float* mean, float* sd, int ld_out, int B,
+                          hipStream_t st);
+// out[row][c] = h[row][c] * gate[b][c] + r[row][c] for row = in_off + t, t < len
+void launch_scale_add_rows_rag(const float* h, int ldh, const float* gate, const float* r, int ldr, float* out, int ldo, const RagSeg* seg,
+                               int max_len, int C, int B, hipStream_t st);
+// out[row] = [x[row] | mean[b] | sd[b]] for row = in_off + t, t < len
+void launch_concat_stats_rag(const float* x, int ldx, const float* mean, const float* sd, const RagSeg* seg, int max_len, int C, float* out,
+                             int B, hipStream_t st);
+// softmax over the clip's own rows in_off .. in_off + len for every (b, c), in place
+void launch_softmax_time_rag(float* a, const RagSeg* seg, int C, int B, hipStream_t st);
 
 // --------------------------------------------------------------------------------- attention.hip
 // Generic row attention over a fused qkv buffer (prefill + codec transformer).

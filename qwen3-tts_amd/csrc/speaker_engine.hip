@@ -41,6 +41,11 @@ struct qtts_speaker {
     std::vector<Blk> blks;
     DevBuf buf[6];
     size_t buf_elems = 0;
+    // ragged batches (embed_ragged): the per-clip row tables of one call.  Table 0 = waveform -> hop rows, 1 = hop rows -> mel frames,
+    // 2 = frames in place, then per distinct reflect padding p > 0 of the config a pair (frames -> padded rows, padded rows -> frames)
+    std::vector<int> rag_pads;
+    std::vector<RagSeg> rag_host;
+    DevBuf rag_dev;
 
     std::vector<float>& P(const std::string& n, std::initializer_list<int64_t> want) {
         auto it = host.find(n);
@@ -90,6 +95,35 @@ struct qtts_speaker {
     }
     void finalize();
     void embed(const float* wav, int B, int S, float* out, float* mels_out, hipStream_t st);
+    void embed_ragged(const float* wav, int B, const int32_t* samples, float* out, float* mels_out, hipStream_t st);
+    const RagSeg* rag_table(int i) const { return rag_dev.as<RagSeg>() + (size_t)i * cfg.max_batch; }
+    void note_pad(const SLin& l) {
+        const int p = l.dil * (l.k - 1) / 2;
+        if (p > 0 && std::find(rag_pads.begin(), rag_pads.end(), p) == rag_pads.end()) rag_pads.push_back(p);
+    }
+    // tdnn() over packed clips: rows = all clips' frames, Tmax = the longest clip's.  The GEMM runs over the packed (padded) rows as ONE
+    // sequence: a tap that reaches back across a clip's first padded row lands in the 2p leading rows the copy drops
+    void tdnn_rag(const SLin& l, const float* src1, int ld1, const float* src2, int ld2, int B, int rows, int Tmax, int act, float* dst,
+                  int ldd, float* scratch_pad, float* scratch_out, hipStream_t st) {
+        const int total = l.dil * (l.k - 1), p = total / 2;
+        if (p == 0 && !src2) {
+            gemm(l, src1, ld1, rows, rows, scratch_out, l.N, st);
+            launch_copy_act_rows(scratch_out, l.N, rows, 0, rows, l.N, act, dst, ldd, 1, st);
+            return;
+        }
+        if (p == 0) {                                                      // (no such layer in ECAPA-TDNN; kept for a complete mapping)
+            launch_reflect_pad_add_rows_rag(src1, ld1, src2, ld2, rag_table(2), Tmax, 0, l.K, scratch_pad, B, st);
+            gemm(l, scratch_pad, l.K, rows, rows, scratch_out, l.N, st);
+            launch_copy_act_rows(scratch_out, l.N, rows, 0, rows, l.N, act, dst, ldd, 1, st);
+            return;
+        }
+        const int j = (int)(std::find(rag_pads.begin(), rag_pads.end(), p) - rag_pads.begin());
+        QTTS_REQUIRE(j < (int)rag_pads.size(), QTTS_ERR_STATE, "speaker: reflect padding without a ragged table");
+        const int prow = rows + 2 * p * B;
+        launch_reflect_pad_add_rows_rag(src1, ld1, src2, ld2, rag_table(3 + 2 * j), Tmax, p, l.K, scratch_pad, B, st);
+        gemm(l, scratch_pad, l.K, prow, prow, scratch_out, l.N, st);
+        launch_copy_act_rows_rag(scratch_out, l.N, rag_table(4 + 2 * j), Tmax, total, l.N, act, dst, ldd, B, st);
+    }
     // y[dst] = act(conv(x)) with reflect "same" padding; x = src1 (+ src2), both strided row views of C = l.K channels
     void tdnn(const SLin& l, const float* src1, int ld1, const float* src2, int ld2, int B, int T, int act, float* dst, int ldd,
               float* scratch_pad, float* scratch_out, hipStream_t st) {
@@ -170,6 +204,10 @@ void qtts_speaker::finalize() {
     per_seq = std::max(per_seq, (size_t)(T + 64) * (size_t)(3 * cl));
     buf_elems = per_seq * (size_t)std::max(1, c.max_batch);
     for (auto& b : buf) b.alloc(buf_elems * sizeof(float));
+    note_pad(tdnn0); note_pad(mfa); note_pad(asp_tdnn);
+    for (auto& b : blks) { note_pad(b.tdnn1); note_pad(b.tdnn2); for (auto& r : b.res) note_pad(r); }
+    rag_host.resize((3 + 2 * rag_pads.size()) * (size_t)std::max(1, c.max_batch));
+    rag_dev.alloc(rag_host.size() * sizeof(RagSeg));
     host.clear();
     finalized = true;
 }
@@ -239,6 +277,104 @@ void qtts_speaker::embed(const float* wav, int B, int S, float* out, float* mels
     gemm(fc, pooled, 2 * cl, B, 1, out, c.enc_dim, st);
 }
 
+// embed() for B clips of DIFFERENT lengths, packed: clip b's samples follow clip b-1's, and so do its hop rows, its mel frames and the
+// rows of every later stage.  Stage for stage the arithmetic of embed(); only the per-sequence kernels read a row table instead of one T.
+void qtts_speaker::embed_ragged(const float* wav, int B, const int32_t* samples, float* out, float* mels_out, hipStream_t st) {
+    const auto& c = cfg;
+    QTTS_REQUIRE(finalized, QTTS_ERR_STATE, "speaker: finalize() first");
+    QTTS_REQUIRE(B >= 1 && B <= c.max_batch, QTTS_ERR_LIMIT,
+                 "speaker: ragged batch of " + std::to_string(B) + " clips outside 1.." + std::to_string(c.max_batch) + " (max_batch given at create)");
+    const int hop = c.hop_size, pad = (c.n_fft - hop) / 2;
+    int pmax = 0;
+    for (int p : rag_pads) pmax = std::max(pmax, p);
+    // ---- every refusal before the first launch
+    for (int b = 0; b < B; ++b)
+        QTTS_REQUIRE(samples[b] >= 1 && samples[b] <= c.max_samples, QTTS_ERR_LIMIT,
+                     "speaker: clip " + std::to_string(b) + " has " + std::to_string(samples[b]) + " samples, outside 1.." +
+                         std::to_string(c.max_samples) + " (max_samples given at create)");
+    for (int b = 0; b < B; ++b) {
+        const int T = (samples[b] + 2 * pad) / hop - (ntap - 1);
+        QTTS_REQUIRE(T >= 1 && samples[b] > pad, QTTS_ERR_ARG,
+                     "speaker: clip " + std::to_string(b) + " (" + std::to_string(samples[b]) + " samples) is shorter than one STFT window");
+        QTTS_REQUIRE(T > pmax, QTTS_ERR_ARG,
+                     "speaker: clip " + std::to_string(b) + " (" + std::to_string(samples[b]) + " samples, " + std::to_string(T) +
+                         " mel frames) is not longer than the widest reflect padding (" + std::to_string(pmax) + " frames)");
+    }
+    // ---- row tables
+    const size_t mb = (size_t)c.max_batch;
+    int woff = 0, roff = 0, toff = 0, Rmax = 0, Tmax = 0;
+    for (int b = 0; b < B; ++b) {
+        const int S = samples[b], R = (S + 2 * pad) / hop, T = R - (ntap - 1);
+        rag_host[0 * mb + b] = RagSeg{woff, roff, S};
+        rag_host[1 * mb + b] = RagSeg{roff, toff, T};
+        rag_host[2 * mb + b] = RagSeg{toff, toff, T};
+        for (size_t j = 0; j < rag_pads.size(); ++j) {
+            const int poff = toff + 2 * rag_pads[j] * b;
+            rag_host[(3 + 2 * j) * mb + b] = RagSeg{toff, poff, T};
+            rag_host[(4 + 2 * j) * mb + b] = RagSeg{poff, toff, T};
+        }
+        woff += S; roff += R; toff += T;
+        Rmax = std::max(Rmax, R); Tmax = std::max(Tmax, T);
+    }
+    const int Rt = roff, Tt = toff;                                                           // packed hop rows, packed mel frames
+    QTTS_CHECK_HIP(hipMemcpyAsync(rag_dev.p, rag_host.data(), rag_host.size() * sizeof(RagSeg), hipMemcpyHostToDevice, st));
+    const RagSeg* seg_wav = rag_table(0); const RagSeg* seg_mel = rag_table(1); const RagSeg* seg = rag_table(2);
+    float* w0 = buf[0].as<float>(); float* w1 = buf[1].as<float>(); float* w2 = buf[2].as<float>();
+    float* w3 = buf[3].as<float>(); float* w4 = buf[4].as<float>(); float* w5 = buf[5].as<float>();
+    // ---- log-mel spectrogram: the DFT's taps that reach back across a clip's first row land in its ntap-1 leading rows, dropped below
+    launch_reflect_rows_1d_rag(wav, seg_wav, pad, Rmax, hop, w0, B, st);                      // w0: [Rt][hop]
+    gemm(dft, w0, hop, Rt, Rt, w1, 2 * nb, st);                                               // w1: [Rt][2*nb] (re | im)
+    launch_magnitude_pad(w1, 2 * nb, nb, w0, Kp, (int64_t)Rt, st);                            // w0: [Rt][Kp]
+    gemm(melw, w0, Kp, Rt, Rt, w1, c.num_mels, st);                                           // w1: [Rt][num_mels]
+    float* mels = w2;                                                                         // [Tt][mel_dim]
+    launch_copy_act_rows_rag(w1, c.num_mels, seg_mel, Tmax, ntap - 1, c.num_mels, ROWACT_LOG_CLAMP, mels, c.mel_dim, B, st);
+    if (mels_out)
+        QTTS_CHECK_HIP(hipMemcpyAsync(mels_out, mels, (size_t)Tt * c.mel_dim * sizeof(float), hipMemcpyDeviceToDevice, st));
+    // ---- ECAPA-TDNN
+    const int nblk = c.n_blocks, C0 = c.channels[0], cl = c.channels[nblk - 1];
+    float* h0 = w3;                                                                           // [Tt][C0]
+    tdnn_rag(tdnn0, mels, c.mel_dim, nullptr, 0, B, Tt, Tmax, ROWACT_RELU, h0, C0, w0, w1, st);
+    float* cat = w4;                                                                          // [Tt][cl]
+    int off = 0;
+    const float* in = h0; int ld_in = C0;
+    for (size_t i = 0; i < blks.size(); ++i) {
+        auto& b = blks[i];
+        const int co = b.tdnn1.N, cw = co / c.res2net_scale;
+        float* h1 = w2;
+        tdnn_rag(b.tdnn1, in, ld_in, nullptr, 0, B, Tt, Tmax, ROWACT_RELU, h1, co, w0, w1, st);
+        float* h2 = w5;
+        launch_copy_act_rows(h1, co, Tt, 0, Tt, cw, ROWACT_NONE, h2, co, 1, st);              // group 0 passes through
+        for (int s = 1; s < c.res2net_scale; ++s)
+            tdnn_rag(b.res[s - 1], h1 + s * cw, co, s >= 2 ? h2 + (s - 1) * cw : nullptr, co, B, Tt, Tmax, ROWACT_RELU, h2 + s * cw, co,
+                     w0, w1, st);
+        float* h3 = w2;
+        tdnn_rag(b.tdnn2, h2, co, nullptr, 0, B, Tt, Tmax, ROWACT_RELU, h3, co, w0, w1, st);
+        float* mean = w0; float* g1 = w0 + (size_t)B * co; float* tmp = w1; float* gate = w5;
+        launch_col_stats_rag(h3, co, nullptr, seg, co, mean, nullptr, co, B, st);             // each clip's own mean over time
+        gemm(b.se1, mean, co, B, 1, tmp, c.se_channels, st);
+        launch_copy_act_rows(tmp, c.se_channels, 1, 0, 1, c.se_channels, ROWACT_RELU, g1, c.se_channels, B, st);
+        gemm(b.se2, g1, c.se_channels, B, 1, tmp, co, st);
+        launch_copy_act_rows(tmp, co, 1, 0, 1, co, ROWACT_SIGMOID, gate, co, B, st);
+        launch_scale_add_rows_rag(h3, co, gate, in, ld_in, cat + off, cl, seg, Tmax, co, B, st);
+        in = cat + off; ld_in = cl; off += co;
+    }
+    // ---- multi-layer feature aggregation + attentive statistics pooling
+    float* x = w3;                                                                            // [Tt][cl]
+    tdnn_rag(mfa, cat, cl, nullptr, 0, B, Tt, Tmax, ROWACT_RELU, x, cl, w0, w1, st);
+    float* mean = w2; float* sd = w2 + (size_t)B * cl;
+    launch_col_stats_rag(x, cl, nullptr, seg, cl, mean, sd, cl, B, st);
+    float* ain = w4;                                                                          // [Tt][3*cl]
+    launch_concat_stats_rag(x, cl, mean, sd, seg, Tmax, cl, ain, B, st);
+    float* a1 = w5;                                                                           // [Tt][attention_channels]
+    tdnn_rag(asp_tdnn, ain, 3 * cl, nullptr, 0, B, Tt, Tmax, ROWACT_RELU_TANH, a1, c.attention_channels, w0, w1, st);
+    float* a2 = w4;                                                                           // [Tt][cl]
+    gemm(asp_conv, a1, c.attention_channels, Tt, Tt, a2, cl, st);
+    launch_softmax_time_rag(a2, seg, cl, B, st);
+    float* pooled = w2;                                                                       // [B][2*cl] = mean | std
+    launch_col_stats_rag(x, cl, a2, seg, cl, pooled, pooled + cl, 2 * cl, B, st);
+    gemm(fc, pooled, 2 * cl, B, 1, out, c.enc_dim, st);
+}
+
 // ============================================================================================ C ABI
 namespace qtts { void set_last_error(const std::string& s); }
 #define QTTS_API_BEGIN try {
@@ -294,6 +430,13 @@ int qtts_speaker_embed(qtts_speaker* s, const float* wav_dev, int32_t B, int32_t
     QTTS_API_BEGIN
     QTTS_REQUIRE(s && wav_dev && emb_dev, QTTS_ERR_ARG, "null argument");
     s->embed(wav_dev, B, samples, emb_dev, mels_dev, (hipStream_t)stream);
+    QTTS_API_END
+}
+int qtts_speaker_embed_ragged(qtts_speaker* s, const float* wav_dev, int32_t B, const int32_t* samples_host, float* emb_dev,
+                              float* mels_dev, void* stream) {
+    QTTS_API_BEGIN
+    QTTS_REQUIRE(s && wav_dev && samples_host && emb_dev, QTTS_ERR_ARG, "null argument");
+    s->embed_ragged(wav_dev, B, samples_host, emb_dev, mels_dev, (hipStream_t)stream);
     QTTS_API_END
 }
 

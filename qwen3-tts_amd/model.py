@@ -259,9 +259,10 @@ class Qwen3TTSForConditionalGeneration:
 
     def extract_speaker_embeddings(self, audios: List[np.ndarray], sr: int) -> List[torch.Tensor]:
         """`extract_speaker_embedding` (M:1941-1954) for a LIST of 24 kHz waveforms -- what `create_voice_clone_prompt` (IM:356-458)
-        computes clip by clip.  Clips of EQUAL length run through the log-mel front end and the ECAPA-TDNN as one batch of up to
-        SPEAKER_BATCH rows, ragged clips are bucketed by exact length (`SpeakerEncoderEngine.embed_many`); the batched rows equal the
-        clip-by-clip ones (GPU test).  The result list is in the order of `audios`."""
+        computes clip by clip.  Up to SPEAKER_BATCH clips run through the log-mel front end and the ECAPA-TDNN as one launch sequence,
+        whatever their lengths: clips of different lengths travel packed, every clip keeps its own paddings and time statistics
+        (`SpeakerEncoderEngine.embed_many` / `embed_ragged`); the batched rows equal the clip-by-clip ones (GPU test).  The result list
+        is in the order of `audios`."""
         assert sr == 24000, "Only support 24kHz audio"
         if not self._speaker_state:
             raise NotImplementedError("this checkpoint has no `speaker_encoder.*` weights (only the Base model does)")
@@ -657,8 +658,8 @@ class Qwen3TTSModel:
         items = []
         spk_sr = int(self.model.speaker_encoder_sample_rate)
         wav24 = [wav if sr == spk_sr else audio_io.resample(wav, sr, spk_sr) for wav, sr in normalized]          # IM:440-444
-        # the reference embeds clip by clip (IM:446-447); here clips of equal length share a launch sequence (round 6: 74 % of this
-        # call was the speaker encoder running eight times) -- a row's embedding does not depend on its neighbours
+        # the reference embeds clip by clip (IM:446-447); here the clips share a launch sequence, of equal length or not (round 6: 74 % of
+        # this call was the speaker encoder running eight times) -- a row's embedding does not depend on its neighbours
         if hasattr(self.model, "extract_speaker_embeddings"):
             spk = self.model.extract_speaker_embeddings(wav24, spk_sr)
         else:                                   # (a model object without the batched entry point: `attach()`-style stand-ins)

@@ -98,6 +98,7 @@ class SpeakerEncoderEngine:
         self.max_batch, self.max_samples = int(max_batch), int(max_samples)
         self._lib = _lib.load_library()
         self._lock = threading.RLock()
+        self.embed_calls = 0                 # C embed calls made (qtts_speaker_embed + qtts_speaker_embed_ragged): which path ran
         c = self.config
         sc = fill_speaker_config(c, compute_dtype, self.max_batch, self.max_samples)
         self._h = C.c_void_p()
@@ -129,24 +130,45 @@ class SpeakerEncoderEngine:
         with torch.cuda.device(self.device):
             _lib.check(self._lib.qtts_speaker_embed(self._h, C.c_void_p(x.data_ptr()), B, S, C.c_void_p(out.data_ptr()), None,
                                                     C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+        self.embed_calls += 1
+        return out
+
+    @_lib.locked
+    def embed_ragged(self, clips) -> torch.Tensor:
+        """A list of at most `max_batch` 1-D waveforms (24 kHz, in [-1, 1]) of ANY lengths -> (B, enc_dim), one launch sequence
+        (qtts_speaker_embed_ragged: the clips travel packed, nothing is padded; row b is what `embed` gives for clip b alone)."""
+        clips = [c if isinstance(c, torch.Tensor) else torch.from_numpy(np.asarray(c, dtype=np.float32)) for c in clips]
+        if not clips or any(c.dim() != 1 for c in clips):
+            raise ValueError("embed_ragged: a non-empty list of 1-D waveforms")
+        B = len(clips)
+        n = (C.c_int32 * B)(*[int(c.shape[0]) for c in clips])
+        x = torch.cat([c.to(self.device, torch.float32) for c in clips]).contiguous()
+        out = torch.empty(B, self.config.enc_dim, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.qtts_speaker_embed_ragged(self._h, C.c_void_p(x.data_ptr()), B, n, C.c_void_p(out.data_ptr()), None,
+                                                           C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+        self.embed_calls += 1
         return out
 
     def embed_many(self, audios) -> list:
-        """A LIST of 24 kHz waveforms -> their x-vectors, in order.  Clips of EQUAL length run as one batch of up to `max_batch` rows
-        (every row keeps its own time statistics -- the squeeze-excitation means and the attentive pooling are per row -- so a row's
-        x-vector does not depend on its neighbours); clips of other lengths form their own groups: padding a clip would change its
-        statistics, so ragged clips are bucketed by exact length."""
+        """A LIST of 24 kHz waveforms -> their x-vectors, in order.  Every row keeps its own time statistics (the reflect paddings, the
+        squeeze-excitation means and the attentive pooling are per clip), so a clip's x-vector does not depend on its neighbours.
+        Clips that ALL share one length run as `embed` batches of up to `max_batch` rows; any other list is ordered by length and cut
+        into groups of `max_batch`, each one `embed_ragged` call (neighbours of similar length keep the row grids tight)."""
         arrs = [np.asarray(a, dtype=np.float32).reshape(-1) for a in audios]
-        groups: Dict[int, list] = {}
-        for i, a in enumerate(arrs):
-            groups.setdefault(a.shape[0], []).append(i)
         out = [None] * len(arrs)
-        for idx in groups.values():
-            for k in range(0, len(idx), self.max_batch):
-                part = idx[k:k + self.max_batch]
-                emb = self.embed(torch.from_numpy(np.stack([arrs[i] for i in part])))
-                for r, i in enumerate(part):
-                    out[i] = emb[r]
+        if len({a.shape[0] for a in arrs}) <= 1:
+            for k in range(0, len(arrs), self.max_batch):
+                emb = self.embed(torch.from_numpy(np.stack(arrs[k:k + self.max_batch])))
+                for r in range(emb.shape[0]):
+                    out[k + r] = emb[r]
+            return out
+        order = sorted(range(len(arrs)), key=lambda i: arrs[i].shape[0])
+        for k in range(0, len(order), self.max_batch):
+            part = order[k:k + self.max_batch]
+            emb = self.embed_ragged([torch.from_numpy(arrs[i]) for i in part])
+            for r, i in enumerate(part):
+                out[i] = emb[r]
         return out
 
     def extract_speaker_embedding(self, audio: np.ndarray, sr: int) -> torch.Tensor:
