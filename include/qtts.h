@@ -662,6 +662,44 @@ typedef struct qtts_row_processors {   /* 32 + 4 x QTTS_PROC_MAX_WORDS bytes; al
 } qtts_row_processors;
 int qtts_talker_set_row_processors(qtts_talker* t, const qtts_row_processors* rows_host, int32_t n_rows);
 
+/* Opt-in FP8 weights for the talker's decode GEMMs (entry points added under ABI 15; no struct changed).  The four Linear operators of
+ * every TALKER layer (q|k|v, o, gate|up, down) are then stored as OCP e4m3fn codes with one power-of-two scale per output row --
+ * half the bytes a frame step streams for them; the code predictor, codec_head, the embeddings and the text projection stay bf16.
+ * The engine is defined without a tolerance: it is, bit for bit, the bf16 engine of another checkpoint W_eff, which
+ * qtts_fp8_effective_rows returns operator by operator (load it into any implementation of the model to judge quality).
+ *   quantizer     w'[n][k] = W[n][k] * g[k] in fp32 (g: the RMSNorm weight folded into the operator, NULL = 1); e[n] = the smallest integer
+ *                 with 448 * 2^e >= max_k |w'[n][k]|, 0 for an all-zero row, clamped to [-100, 100]; code = RNE_e4m3fn(w' * 2^-e).  NaN
+ *                 codes are never produced.  Under the clamp the construction's guarantees end: a row whose maximum exceeds 448 * 2^100
+ *                 (5.7e32) has its larger values SATURATED to +-448 * 2^100, a row below 2^-9 * 2^-100 becomes zero, and a non-finite
+ *                 weight is not supported.  The bitwise identity with the bf16 kernel on d further assumes that no product x * code
+ *                 and no partial sum leaves fp32's normal range in either form (the two differ by the factor 2^e until the
+ *                 epilogue); |e| <= 100 leaves 26 binades on either side, and trained weights sit near e = -12.  d[n][k] = code * 2^e is exactly a bf16 number, and the decode kernels convert the codes to
+ *                 bf16 in registers and run the bf16 kernels' MFMA chains in the bf16 kernels' order: their output is the bf16 kernel's
+ *                 on d.  The talker's row-major prefill operators are built from W_eff[n][k] = fl32(d[n][k] / g[k]) (W[n][k] where
+ *                 g[k] == 0), so prompt and decode steps see one model.
+ *   set_weight_format  between create and finalize, like qtts_talker_set_kv_pool.  QTTS_WEIGHTS_DEFAULT (0): the engine as it is;
+ *                 QTTS_WEIGHTS_FP8 on a bf16 engine only (QTTS_ERR_ARG on an fp32 engine or an unknown value, QTTS_ERR_STATE after finalize).
+ *   weight_format the format, and (after finalize) the bytes of all packed decode operators the engine holds on the device: an fp8
+ *                 operator counts N * K + 4 N where its bf16 form counts 2 N K.  Either pointer may be NULL.
+ *   The two fp8 calls are host-only (no device is touched).  codes: N x K bytes, exps: N. */
+#define QTTS_WEIGHTS_DEFAULT 0
+#define QTTS_WEIGHTS_FP8 1
+int qtts_talker_set_weight_format(qtts_talker* t, int32_t fmt);
+int qtts_talker_weight_format(qtts_talker* t, int32_t* fmt_host, int64_t* packed_bytes_host);
+int qtts_fp8_quantize_rows(const float* W /* (N, K) */, const float* g_or_null /* (K) */, int32_t N, int32_t K, uint8_t* codes, int32_t* exps);
+int qtts_fp8_effective_rows(const float* W /* (N, K) */, const float* g_or_null /* (K) */, int32_t N, int32_t K, float* W_eff);
+/* Test hook: ONE launch of the decode GEMM on HOST operands (device memory is allocated, filled, and read back inside the call).
+ *   out[M][No] = epilogue(rstd[m] * sum_k bf16(x[m][k]) * P[n][k]), P = the operator packed from W (x g when given) with `fs` features per
+ *   strip, as bf16 (fmt 0) or as fp8 codes + scales (fmt QTTS_WEIGHTS_FP8).  W is given in PACKED row order (the caller interleaves
+ *   gate / up rows for act 2 = SwiGLU strip pairs, 5 = SwiGLU of one strip).  No = N / 2 with a SwiGLU act, else N; out / res / out16
+ *   have leading dimension ldo >= No (columns beyond No are never written); out16 (bf16 bits, NULL = none) is the kernel's bf16 shadow.
+ *   last_decode_gemm_kernel: the kernel family that call ran on the calling thread: 2 skinny2_kernel, 8 skinny8_kernel (the batch <= 8 form),
+ *   + 16 for their fp8 forms, 0 any other. */
+int qtts_debug_last_decode_gemm_kernel(int32_t* kind_host);
+int qtts_debug_decode_gemm(const float* x /* (M, K) */, const float* W /* (N, K) */, const float* g_or_null, const float* bias_or_null /* (N) */,
+                           const float* res_or_null /* (M, ldo) */, int32_t M, int32_t N, int32_t K, int32_t fs, int32_t norm, int32_t act,
+                           int32_t fmt, int32_t ldo, float* out /* (M, ldo) in/out */, uint16_t* out16_or_null /* (M, ldo) in/out */);
+
 /* Test/diagnostic hooks (device -> caller device buffers, after prefill / a generate call). */
 int qtts_talker_debug_logits(qtts_talker* t, float* logits_dev /* (B, vocab) */, void* stream);
 /* The talker cache's page table of one row (0 <= row < max_batch) as it stands on the DEVICE -- what the next launch on `stream` reads:

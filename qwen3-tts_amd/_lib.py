@@ -115,6 +115,7 @@ class GemmClassC(C.Structure):
 
 
 ABI_VERSION = 15          # include/qtts.h; bumped on any signature change
+WEIGHTS_DEFAULT, WEIGHTS_FP8 = 0, 1      # include/qtts.h QTTS_WEIGHTS_*
 
 # every symbol include/qtts.h declares (checked by tests/test_host_logic.py::test_abi_exports_every_declared_symbol without a GPU)
 SYMBOLS = ["qtts_last_error", "qtts_abi_version", "qtts_set_option", "qtts_get_option", "qtts_codec_create", "qtts_codec_destroy", "qtts_codec_bind",
@@ -133,9 +134,13 @@ SYMBOLS = ["qtts_last_error", "qtts_abi_version", "qtts_set_option", "qtts_get_o
            "qtts_talker_stream_begin_admitting_rows", "qtts_talker_stream_row_lens", "qtts_talker_stream_mode",
            "qtts_talker_set_kv_pool", "qtts_talker_stream_kv", "qtts_talker_stream_evict",
            "qtts_talker_set_row_warpers", "qtts_talker_sampler_class", "qtts_talker_set_row_processors",
+           "qtts_talker_set_weight_format", "qtts_talker_weight_format", "qtts_debug_decode_gemm", "qtts_debug_last_decode_gemm_kernel",
            "qtts_talker_debug_logits", "qtts_talker_debug_kv_table", "qtts_talker_debug_cp_logits", "qtts_talker_get_stats", "qtts_talker_get_gemm_profile", "qtts_talker_set_teacher",
            "qtts_talker_set_profile"]
 
+
+# ... and the two whose names carry a digit (the header scan of that test reads letters and underscores only): required all the same
+SYMBOLS_FP8 = ["qtts_fp8_quantize_rows", "qtts_fp8_effective_rows"]
 
 PRODUCT_LIBRARY = os.path.join(_HERE, "libqtts.so")
 
@@ -174,7 +179,7 @@ def load_library():
     if not os.path.exists(path):
         raise QttsError(-100, f"{path} not found -- run `python qwen3-tts_amd/build.py` (or __graft_entry__.build())")
     lib = C.CDLL(path)
-    missing = [s for s in SYMBOLS if not hasattr(lib, s)]
+    missing = [s for s in SYMBOLS + SYMBOLS_FP8 if not hasattr(lib, s)]
     if missing:          # (entry points added without a version bump: a stale build shows here)
         raise QttsError(-101, f"{path} does not export {', '.join(missing)}; rebuild")
     vp, i32, i64p, f32p = C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.c_void_p
@@ -235,6 +240,12 @@ def load_library():
     lib.qtts_talker_stream_kv.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     lib.qtts_talker_stream_evict.argtypes = [vp, i32, C.POINTER(C.c_int32)]
     lib.qtts_talker_debug_kv_table.argtypes = [vp, i32, C.POINTER(C.c_int32), vp]
+    lib.qtts_talker_set_weight_format.argtypes = [vp, i32]
+    lib.qtts_talker_weight_format.argtypes = [vp, C.POINTER(C.c_int32), i64p]
+    lib.qtts_fp8_quantize_rows.argtypes = [vp, vp, i32, i32, vp, vp]
+    lib.qtts_fp8_effective_rows.argtypes = [vp, vp, i32, i32, vp]
+    lib.qtts_debug_last_decode_gemm_kernel.argtypes = [C.POINTER(C.c_int32)]
+    lib.qtts_debug_decode_gemm.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp]
     lib.qtts_talker_set_row_warpers.argtypes = [vp, C.POINTER(RowWarpersC), i32]
     lib.qtts_talker_set_row_processors.argtypes = [vp, C.POINTER(RowProcessorsC), i32]
     lib.qtts_talker_sampler_class.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
@@ -249,7 +260,7 @@ def load_library():
     lib.qtts_talker_get_gemm_profile.argtypes = [vp, C.POINTER(GemmClassC), i32, C.POINTER(C.c_int32)]
     lib.qtts_talker_set_teacher.argtypes = [vp, vp, i32, vp, vp, vp]
     lib.qtts_talker_set_profile.argtypes = [vp, i32]
-    for s in SYMBOLS:
+    for s in SYMBOLS + SYMBOLS_FP8:
         if s not in ("qtts_last_error", "qtts_codec_destroy", "qtts_talker_destroy", "qtts_encoder_destroy",
                      "qtts_speaker_destroy"):
             getattr(lib, s).restype = C.c_int

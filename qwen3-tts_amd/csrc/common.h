@@ -86,6 +86,32 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef short bf16x8 __attribute__((ext_vector_type(8)));  // 8 bf16 = 4 VGPRs (MFMA operand type)
 typedef short bf16x4 __attribute__((ext_vector_type(4)));
 
+// ------------------------------------------------------------------------------------------ fp8 (OCP e4m3fn) weight codes
+// One code -> the bits of the same number as bf16 (exact: 4 exponent bits and 3 of mantissa fit, subnormals m * 2^-9 included).
+// The host's quantizer and the emulator use this; the device converts pairs in hardware (below).
+__host__ __device__ inline bf16_t e4m3_to_bf16_bits(unsigned c) {
+    const unsigned s = (c & 0x80u) << 8, E = (c >> 3) & 15u, m = c & 7u;
+    if (E == 0) {
+        if (m == 0) return (bf16_t)s;
+        const unsigned sh = m >= 4 ? 0u : (m >= 2 ? 1u : 2u);      // leading one of m to bit 2
+        return (bf16_t)(s | ((120u - sh) << 7) | (((m << sh) & 3u) << 5));
+    }
+    if (E == 15 && m == 7) return (bf16_t)(s | 0x7fc0u);            // NaN (the quantizer never produces it)
+    return (bf16_t)(s | ((E + 120u) << 7) | (m << 4));
+}
+// four codes of one dword -> two dwords of packed bf16 (codes 0, 1 -> lo; 2, 3 -> hi): v_cvt_scalef32_pk_bf16_fp8 with scale 1
+__device__ inline void e4m3x4_to_bf16x4(unsigned c, unsigned& lo, unsigned& hi) {
+#ifdef QTTS_HOST_EMU
+    lo = (unsigned)e4m3_to_bf16_bits(c & 0xffu) | ((unsigned)e4m3_to_bf16_bits((c >> 8) & 0xffu) << 16);
+    hi = (unsigned)e4m3_to_bf16_bits((c >> 16) & 0xffu) | ((unsigned)e4m3_to_bf16_bits(c >> 24) << 16);
+#else
+    hwbf16x2 a = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(c, 1.0f, false);
+    hwbf16x2 b = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(c, 1.0f, true);
+    lo = *reinterpret_cast<unsigned*>(&a);
+    hi = *reinterpret_cast<unsigned*>(&b);
+#endif
+}
+
 // ------------------------------------------------------------------------------------------ cross-lane reductions
 // DPP row rotations (VALU rate) instead of ds_bpermute shuffles (LDS crossbar, ~100 cycles each) for the reductions the
 // hot kernels run per key / per row: after ror 8/4/2/1 every lane of a 16-lane row holds the row's sum.

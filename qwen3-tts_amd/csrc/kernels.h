@@ -93,8 +93,18 @@ struct SkinnyParams {
     int* ks_err; int* ks_latch;  // raised by a reducer that gave up (the engine's flag, the generation's stop flag)
     const int* done_flag;        // optional device flag: when non-zero the kernel exits early
     int ablate;                  // `ablate` build variant only (-DQTTS_ABLATE; must be 0 in the product build): 1 no done check, 2 no x loads, 4 no epilogue loads, 8 no weight loads
+    // fp8 weights (opt-in, bf16 engines; M <= 64, bf16 x): Wp holds OCP e4m3fn codes (pack_skinny_weight_fp8), one power-of-two scale per
+    // packed output row.  The kernels convert 8 codes to 8 bf16 in registers and feed the same MFMA chains in the same order as the bf16
+    // form of the same instantiation; the fp32 sums are multiplied by the row's scale in the epilogue (exact): the output is, bit for bit,
+    // the bf16 kernel's on the operator d[n][k] = code * scale[n].
+    int wfmt;                    // 0: Wp as described above; SKINNY_W_FP8: e4m3fn codes
+    const float* wscale;         // [N] 2^e[n] per packed output row (with wfmt)
 };
+constexpr int SKINNY_W_FP8 = 1;
 void launch_skinny(const SkinnyParams& p, bool bf16, hipStream_t st);
+// the kernel family the calling thread's last launch_skinny ran: skinny2_kernel | skinny8_kernel (| SKINNY_KERNEL_FP8: their fp8 forms), or another
+enum { SKINNY_KERNEL_OTHER = 0, SKINNY_KERNEL_2 = 2, SKINNY_KERNEL_8 = 8, SKINNY_KERNEL_FP8 = 16 };
+int skinny_last_kernel();
 void skinny_set_launch_events(hipEvent_t start, hipEvent_t stop);   // (bench.py's roofline leg: time the NEXT launch on its own; null = off)
 constexpr int SKINNY_MAX_ROWS = 128;                 // 65..128 rows: skinny_wide_kernel / the fp32 kernel's 8-tile form (pass 0 of the code predictor at batch 33..64)
 bool skinny_takes_bf16_x(int M, int K, bool bf16);   // bf16 mode: any M <= 128, K % 32 == 0
@@ -106,6 +116,15 @@ size_t skinny_packed_bytes(int N, int K, bool bf16);
 // Pack W[N][K] (row-major f32), optionally scaled per input column by g[K], into the streaming tile layout;
 // gate/up interleaving is the caller's.
 void pack_skinny_weight(const float* W, int N, int K, bool bf16, void* out_host, const float* g = nullptr, int fs = 16);
+// fp8 form.  The row quantizer (include/qtts.h: qtts_fp8_quantize_rows): w' = W[n][k] * g[k] in fp32, e[n] = the smallest integer with
+// 448 * 2^e >= max_k |w'| (0 for an all-zero row, clamped to [-100, 100]), code = RNE_e4m3fn(w' * 2^-e).
+void fp8_quantize_rows(const float* W, const float* g, int N, int K, uint8_t* codes /* [N][K] */, int32_t* exps /* [N] */);
+// W_eff[n][k] = fl32(code * 2^e / g[k]) (W[n][k] where g[k] == 0): the checkpoint whose bf16 engine IS the fp8 engine
+void fp8_effective_rows(const float* W, const float* g, int N, int K, float* W_eff);
+// Code layout by strip width: fs 8 | 4: tiles [N/fs][K/32][4 k-slices][fs features][8 B]; fs 16: tile PAIRS
+// [N/16][ceil(K/64)][4 k-slices][16 features][8 B even tile | 8 B odd tile] (an odd last tile is padded with zero codes).
+size_t skinny_fp8_code_bytes(int N, int K, int fs);
+void pack_skinny_weight_fp8(const float* W, int N, int K, void* codes_out, float* scales_out /* [N] = 2^e */, const float* g = nullptr, int fs = 16);
 
 // --------------------------------------------------------------------------------- elementwise.hip
 void launch_rmsnorm(const float* x, int ldx, const float* w, float eps, float* y, int ldy, int rows, int C,

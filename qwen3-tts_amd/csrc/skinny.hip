@@ -49,6 +49,9 @@ namespace qtts {
 // times -- what rocprofv3's kernel trace reports), so that every launch of the REAL frame step is timed on its own.
 static thread_local hipEvent_t tl_ev_start = nullptr, tl_ev_stop = nullptr;
 void skinny_set_launch_events(hipEvent_t start, hipEvent_t stop) { tl_ev_start = start; tl_ev_stop = stop; }
+// which kernel family the last launch_skinny call of this thread ran (tests: a shape meant for the batch <= 8 kernel must not pass on another one)
+static thread_local int tl_last_kernel = 0;
+int skinny_last_kernel() { return tl_last_kernel; }
 #define QTTS_SK_LAUNCH(kern, grid, block, lds, st, ...)                                                               \
     do {                                                                                                              \
         if (tl_ev_start) hipExtLaunchKernelGGL(kern, grid, block, lds, st, tl_ev_start, tl_ev_stop, 0, __VA_ARGS__);  \
@@ -56,9 +59,25 @@ void skinny_set_launch_events(hipEvent_t start, hipEvent_t stop) { tl_ev_start =
     } while (0)
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 template <class T>
 __device__ inline T skinny_wload(const T* ptr) { return __builtin_nontemporal_load(ptr); }
+
+// fp8 weights (SkinnyParams::wfmt): 8 e4m3fn codes (k ascending) -> the MFMA A-operand image of the same 8 numbers as bf16.  Exact, so
+// everything downstream of it is the bf16 kernel's arithmetic.
+__device__ inline u32x4 e4m3x8_to_bf16x8(unsigned c0, unsigned c1) {
+    u32x4 r;
+    unsigned a, b;
+    e4m3x4_to_bf16x4(c0, a, b); r[0] = a; r[1] = b;
+    e4m3x4_to_bf16x4(c1, a, b); r[2] = a; r[3] = b;
+    return r;
+}
+// a weight request's register image: 16 B of bf16, or 8 B of codes
+template <bool W8> struct SkinnyWReg { typedef u32x4 type; };
+template <> struct SkinnyWReg<true> { typedef u32x2 type; };
+__device__ inline u32x4 skinny_wa(const u32x4& w) { return w; }
+__device__ inline u32x4 skinny_wa(const u32x2& w) { return e4m3x8_to_bf16x8(w[0], w[1]); }
 
 __device__ inline void skinny_store4(const SkinnyParams& p, int row, int col, const f32x4& o, bool shadow) {
     if (shadow && p.out16) {
@@ -80,8 +99,13 @@ __device__ inline void skinny_store4(const SkinnyParams& p, int row, int col, co
 // requests; the generic variant guards the tail tile by tile (tiny test dimensions, odd K).
 // NCH > 0 (EXACT only): the number of chunks is a compile-time constant (1..3) and the whole kernel is straight-line code -- no
 // branch, hence no register merge (a merge copy of a load result waits for that load) between the request bursts.
-template <int MT, int SPW, int NW, int FS, bool XB16, int U, bool EXACT, int NCH>
-__global__ __launch_bounds__(NW * 64) void skinny2_kernel(SkinnyParams p) {
+// W8 (fp8 weights, opt-in): the kernel's body is shared with the fp8 form (skinny2_fp8_kernel below).  A weight request is then 8 B of
+// e4m3fn codes per lane -- the same (wave, tile, lane, element) assignment, converted to the bf16 operand right in front of its MFMA --
+// and the combined sums take the row's power-of-two scale before rstd.  16-feature strips hold their tiles in interleaved PAIRS (the
+// batch <= 8 kernel's unit, see pack_skinny_weight_fp8): tile kt is the half kt & 1 of the 16-B entries of pair kt >> 1.
+template <int MT, int SPW, int NW, int FS, bool XB16, int U, bool EXACT, int NCH, bool W8>
+__device__ __forceinline__ void skinny2_body(SkinnyParams& p) {
+    typedef typename SkinnyWReg<W8>::type wreg;
     constexpr int KT = 32;                                       // k per tile
     constexpr int NS = SPW * MT + MT;                            // accumulators per wave: the GEMM's + one X.X^T per m-tile
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_sk[];
@@ -111,10 +135,13 @@ __global__ __launch_bounds__(NW * 64) void skinny2_kernel(SkinnyParams p) {
     // branch per load; the other lanes hold zeros, and what they feed to the MFMA only reaches output rows / columns nobody
     // stores.
     const bool wlane = lj < FS;
-    const u32x4* wbase[SPW];
+    constexpr bool WPAIR = W8 && FS == 16;                       // fp8, 16-feature strips: tile pairs, 16 B per (k-slice, feature)
+    const wreg* wbase[SPW];
 #pragma unroll
-    for (int s = 0; s < SPW; ++s)
-        wbase[s] = reinterpret_cast<const u32x4*>(p.Wp) + ((size_t)(strip0 + s) * nkt) * (FS * 4) + lq * FS + (wlane ? lj : 0);
+    for (int s = 0; s < SPW; ++s) {
+        if constexpr (WPAIR) wbase[s] = reinterpret_cast<const wreg*>(p.Wp) + ((size_t)(strip0 + s) * ((nkt + 1) >> 1) * 64 + lq * 16 + lj) * 2;
+        else wbase[s] = reinterpret_cast<const wreg*>(p.Wp) + ((size_t)(strip0 + s) * nkt) * (FS * 4) + lq * FS + (wlane ? lj : 0);
+    }
     // B operand of tile kt, m-tile m: lane (lj, lq) <- x[m*16 + lj][kt*32 + lq*8 .. +8]
     const unsigned short* xp16[MT];
     const float* xp32[MT];
@@ -133,7 +160,10 @@ __global__ __launch_bounds__(NW * 64) void skinny2_kernel(SkinnyParams p) {
 
     // (non-temporal: measured twice -- round 1 whole-frame +7.6 % with plain loads; round 2 per GEMM class, plain loads for the code
     // predictor's re-read 157 MB: no gain with, +3.5 % without a warm-up -- profiles/r02_ab_inproc_prefetch_temporal.json)
-    auto wload = [&](const u32x4* ptr) -> u32x4 { return skinny_wload(ptr); };
+    auto wload = [&](int s, int kt) -> wreg {
+        if constexpr (WPAIR) return skinny_wload(wbase[s] + (size_t)(kt >> 1) * 128 + (kt & 1));
+        else return skinny_wload(wbase[s] + (size_t)kt * wstep);
+    };
     auto load_x = [&](int m, int kt) -> u32x4 {
         if constexpr (XB16) return *reinterpret_cast<const u32x4*>(xp16[m] + kt * xstep);
         else {    // fp32 x (no bf16 copy from the producer): converted here; not on the frame step's hot path
@@ -147,13 +177,13 @@ __global__ __launch_bounds__(NW * 64) void skinny2_kernel(SkinnyParams p) {
     };
     // (the operand registers are zeroed ONCE, below: lanes outside the masks never write them again, so a masked request is an
     // in-place update and needs no merge copy -- a copy would wait for the load it copies)
-    auto load_chunk = [&](u32x4 (&w)[SPW][U], u32x4 (&xq)[MT][U], int c) {
+    auto load_chunk = [&](wreg (&w)[SPW][U], u32x4 (&xq)[MT][U], int c) {
         if constexpr (EXACT) {
             if (FS == 16 || wlane) {                             // one exec mask for all weight requests of the chunk
 #pragma unroll
                 for (int u = 0; u < U; ++u)
 #pragma unroll
-                    for (int s = 0; s < SPW; ++s) w[s][u] = wload(wbase[s] + (size_t)(wave + NW * (c * U + u)) * wstep);
+                    for (int s = 0; s < SPW; ++s) w[s][u] = wload(s, wave + NW * (c * U + u));
             }
 #pragma unroll
             for (int m = 0; m < MT; ++m)
@@ -169,7 +199,7 @@ __global__ __launch_bounds__(NW * 64) void skinny2_kernel(SkinnyParams p) {
                     const int kt = wave + NW * (c * U + u);
                     if (wlane) {
 #pragma unroll
-                        for (int s = 0; s < SPW; ++s) w[s][u] = wload(wbase[s] + (size_t)kt * wstep);
+                        for (int s = 0; s < SPW; ++s) w[s][u] = wload(s, kt);
                     }
 #pragma unroll
                     for (int m = 0; m < MT; ++m)
@@ -183,13 +213,14 @@ __global__ __launch_bounds__(NW * 64) void skinny2_kernel(SkinnyParams p) {
     // has its own registers and is requested right here (up to 24 KiB per wave in flight); the generic kernel keeps two chunks
     // in flight and ping-pongs.
     constexpr int NSET = NCH > 0 ? NCH : 2;
-    u32x4 wR[NSET][SPW][U], xR[NSET][MT][U];
+    wreg wR[NSET][SPW][U];
+    u32x4 xR[NSET][MT][U];
 #pragma unroll
     for (int k = 0; k < NSET; ++k)
 #pragma unroll
         for (int u = 0; u < U; ++u) {
 #pragma unroll
-            for (int s = 0; s < SPW; ++s) wR[k][s][u] = (u32x4){0u, 0u, 0u, 0u};
+            for (int s = 0; s < SPW; ++s) wR[k][s][u] = wreg{};
 #pragma unroll
             for (int m = 0; m < MT; ++m) xR[k][m][u] = (u32x4){0u, 0u, 0u, 0u};
         }
@@ -202,13 +233,17 @@ __global__ __launch_bounds__(NW * 64) void skinny2_kernel(SkinnyParams p) {
     }
 
     // ---- 2. epilogue operands of wave 0 are fetched now, under the weight stream
-    f32x4 resv[SPW][MT], biasv[SPW];
+    f32x4 resv[SPW][MT], biasv[SPW], scv[W8 ? SPW : 1];
     const bool epi_loads = wave == 0 && !QTTS_ABL(p, 4);
 #pragma unroll
     for (int s = 0; s < SPW; ++s) {
         const int col = (p.act == ACT_SWIGLU ? blockIdx.x * 16 : (strip0 + s) * FS) + lq * 4;
         biasv[s] = (f32x4){0.f, 0.f, 0.f, 0.f};
         if (epi_loads && p.bias && lq * 4 < FS) biasv[s] = *reinterpret_cast<const f32x4*>(p.bias + (strip0 + s) * FS + lq * 4);
+        if constexpr (W8) {                                      // the rows' power-of-two scales
+            scv[s] = (f32x4){1.f, 1.f, 1.f, 1.f};
+            if (wave == 0 && lq * 4 < FS) scv[s] = *reinterpret_cast<const f32x4*>(p.wscale + (strip0 + s) * FS + lq * 4);
+        }
 #pragma unroll
         for (int m = 0; m < MT; ++m) {
             resv[s][m] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -222,7 +257,10 @@ __global__ __launch_bounds__(NW * 64) void skinny2_kernel(SkinnyParams p) {
     if (done) return;
     QTTS_TS_DRAINED(2);                    // ... and has arrived
 
-    auto compute_tile = [&](u32x4 (&w)[SPW][U], u32x4 (&xq)[MT][U], int u) {
+    auto compute_tile = [&](wreg (&w)[SPW][U], u32x4 (&xq)[MT][U], int u) {
+        u32x4 wv[SPW];                                           // (fp8: converted once per tile, in front of its MFMAs)
+#pragma unroll
+        for (int s = 0; s < SPW; ++s) wv[s] = skinny_wa(w[s][u]);
 #pragma unroll
         for (int m = 0; m < MT; ++m) {
             bf16x8 xb;
@@ -230,13 +268,13 @@ __global__ __launch_bounds__(NW * 64) void skinny2_kernel(SkinnyParams p) {
 #pragma unroll
             for (int s = 0; s < SPW; ++s) {
                 bf16x8 wa;
-                *reinterpret_cast<u32x4*>(&wa) = w[s][u];
+                *reinterpret_cast<u32x4*>(&wa) = wv[s];
                 acc[s][m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa, xb, acc[s][m], 0, 0, 0);
             }
             if (p.norm) acc_ss[m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xb, xb, acc_ss[m], 0, 0, 0);
         }
     };
-    auto compute_chunk = [&](u32x4 (&w)[SPW][U], u32x4 (&xq)[MT][U], int c) {
+    auto compute_chunk = [&](wreg (&w)[SPW][U], u32x4 (&xq)[MT][U], int c) {
         if constexpr (EXACT) {
 #pragma unroll
             for (int u = 0; u < U; ++u) compute_tile(w, xq, u);
@@ -294,6 +332,7 @@ __global__ __launch_bounds__(NW * 64) void skinny2_kernel(SkinnyParams p) {
             f32x4 t = red[(0 * NS + s * MT + m) * 64 + lane];
 #pragma unroll
             for (int w2 = 1; w2 < NW; ++w2) t += red[(w2 * NS + s * MT + m) * 64 + lane];
+            if constexpr (W8) t = t * scv[s];                    // 2^e[n]: exact, and what the bf16 kernel's sums over d are
             v[s] = t * rstd + biasv[s];
         }
         if (row >= p.M || lq * 4 >= FS) continue;
@@ -312,6 +351,15 @@ __global__ __launch_bounds__(NW * 64) void skinny2_kernel(SkinnyParams p) {
     }
     QTTS_TS_DRAINED(5);                    // stores acknowledged
     QTTS_TS_END(skinny, 0, p.K, p.N);
+}
+template <int MT, int SPW, int NW, int FS, bool XB16, int U, bool EXACT, int NCH>
+__global__ __launch_bounds__(NW * 64) void skinny2_kernel(SkinnyParams p) {
+    skinny2_body<MT, SPW, NW, FS, XB16, U, EXACT, NCH, false>(p);
+}
+// fp8 weights: x is always the producer's bf16 copy (the talker's decode hands it over that way)
+template <int MT, int SPW, int NW, int FS, int U, bool EXACT, int NCH>
+__global__ __launch_bounds__(NW * 64) void skinny2_fp8_kernel(SkinnyParams p) {
+    skinny2_body<MT, SPW, NW, FS, true, U, EXACT, NCH, true>(p);
 }
 
 // ------------------------------------------------------------------------------------------ bf16, 65..128 rows (pass 0 of the code predictor at batch 33..64)
@@ -710,19 +758,24 @@ __device__ inline u32x4 dpp_ror8(const u32x4& v) {
     return r;
 }
 
+// W8 (fp8 weights, opt-in; skinny8_fp8_kernel below shares this body): a tile pair of e4m3fn codes is HALF the bytes and, for 16-feature
+// strips, ONE request where the bf16 form has two -- the pair is stored as [4 k-slices][16 features][8 B even tile | 8 B odd tile], so lane
+// (lj, lq)'s 16 B carry what `we` and `wo` carry below.  8-feature strips keep two 256-B tiles side by side: the same lane-to-entry map
+// as the bf16 form with 8-B entries, converted once and rotated for the odd tile.  Same pairs per wave, same MFMA order, same combine;
+// the row scales 2^e[n] are requested with the other epilogue operands and multiply the combined sums (exact) in front of rstd.
 // Kernel arguments (round 3, measured -2.7 % per frame, profiles/r03_ab_kpre.md): a by-value struct argument is never preloaded into
 // SGPRs by the compiler's kernarg-preload feature (`-mllvm -amdgpu-kernarg-preload-count=16`, build.py FLAGS: the first 14 dwords
 // of SCALAR arguments arrive in user SGPRs with the wave -- no `s_load` round trip in front of the first address computation).
 // So the operands every request of the launch depends on travel as leading scalar arguments (5 pointers + 4 ints = 14 dwords);
 // the struct follows and is only read by the epilogue.
 #define QTTS_SK8_ARGS(p) (p).Wp, (p).x, (p).done_flag, (p).res, (p).bias, (p).ldx, (p).M, (p).K, (p).ldr, (p)
-template <int SPW, int FS, int NP, bool NORM, int NW = 8>
-__global__ __launch_bounds__(NW * 64) void skinny8_kernel(const void* kWp, const float* kx, const int* kdone, const float* kres, const float* kbias,
-                                                          int kldx, int kM, int kK, int kldr, SkinnyParams p) {
-    p.Wp = kWp; p.x = kx; p.done_flag = kdone; p.res = kres; p.bias = kbias; p.ldx = kldx; p.M = kM; p.K = kK; p.ldr = kldr;
+template <int SPW, int FS, int NP, bool NORM, int NW, bool W8>
+__device__ __forceinline__ void skinny8_body(SkinnyParams& p) {
     static_assert(FS == 16 || (FS == 8 && SPW == 1), "skinny8: strips of 16 features, or single strips of 8");
     constexpr int NS = SPW + 1;
-    constexpr int WPP = FS == 16 ? 2 : 1;                        // weight requests per pair and strip (1 KiB each)
+    constexpr int WPP = (FS == 16 && !W8) ? 2 : 1;               // weight requests per pair and strip (1 KiB each; fp8, 8 features: 512 B)
+    constexpr int FSU = (FS == 16 && W8) ? 8 : FS;               // a pair is 8 FSU entries of the request's width
+    typedef typename SkinnyWReg<(W8 && FS == 8)>::type wreg;     // fp8: 16 B (both tiles of a lane) for 16 features, 8 B for 8
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_sk[];
     f32x4* red = reinterpret_cast<f32x4*>(smem_sk);              // [NW][NS][64]
     QTTS_TS_BEGIN();
@@ -734,28 +787,29 @@ __global__ __launch_bounds__(NW * 64) void skinny8_kernel(const void* kWp, const
     const int strip0 = blockIdx.x * SPW;
 
     // 16-B units; a pair of tiles is 2 x FS x 4 units
-    const u32x4* wb[SPW];
+    const wreg* wb[SPW];
 #pragma unroll
     for (int s = 0; s < SPW; ++s)
-        wb[s] = reinterpret_cast<const u32x4*>(p.Wp) + (size_t)(strip0 + s) * nkt * (FS * 4)
-                + (FS == 16 ? lq * 16 + lj : (lj >> 3) * 32 + lq * 8 + (lj & 7)) + (size_t)wave * (FS * 8);
+        wb[s] = reinterpret_cast<const wreg*>(p.Wp) + (size_t)(strip0 + s) * nkt * (FSU * 4)
+                + (FS == 16 ? lq * 16 + lj : (lj >> 3) * 32 + lq * 8 + (lj & 7)) + (size_t)wave * (FSU * 8);
     const unsigned short* xb = reinterpret_cast<const unsigned short*>(p.x) + (size_t)((lj & 7) < p.M ? (lj & 7) : 0) * p.ldx
                                + (lq + 4 * (lj >> 3)) * 8 + wave * 64;
 
     // ---- 1. every request of the launch, back to back: pair i of this wave = tiles 2 (wave + 8 i), + 1
-    u32x4 wR[NP][SPW][WPP], xR[NP];
+    wreg wR[NP][SPW][WPP];
+    u32x4 xR[NP];
 #pragma unroll
     for (int i = 0; i < NP; ++i) {
 #pragma unroll
         for (int s = 0; s < SPW; ++s)
 #pragma unroll
-            for (int h = 0; h < WPP; ++h) wR[i][s][h] = skinny_wload(wb[s] + (size_t)i * (NW * FS * 8) + h * 64);
+            for (int h = 0; h < WPP; ++h) wR[i][s][h] = skinny_wload(wb[s] + (size_t)i * (NW * FSU * 8) + h * 64);
         xR[i] = *reinterpret_cast<const u32x4*>(xb + i * (NW * 64));
     }
     // epilogue operands (used by wave 0 only; requested by every wave so that no branch surrounds a load)
     const int colq = lq * 4 < FS ? lq * 4 : 0;
     const int rowc = lj < p.M ? lj : 0;
-    f32x4 resv[SPW], biasv[SPW];
+    f32x4 resv[SPW], biasv[SPW], scv[W8 ? SPW : 1];
 #pragma unroll
     for (int s = 0; s < SPW; ++s) {
         const int col = p.act == ACT_SWIGLU8 ? blockIdx.x * 8 + (lq & 1) * 4
@@ -764,6 +818,7 @@ __global__ __launch_bounds__(NW * 64) void skinny8_kernel(const void* kWp, const
         const float* rp = p.res ? p.res + (size_t)rowc * p.ldr + col : reinterpret_cast<const float*>(p.x);
         biasv[s] = *reinterpret_cast<const f32x4*>(bp);
         resv[s] = *reinterpret_cast<const f32x4*>(rp);
+        if constexpr (W8) scv[s] = *reinterpret_cast<const f32x4*>(p.wscale + (strip0 + s) * FS + colq);     // the rows' scales (always present)
     }
     const int done = p.done_flag ? *p.done_flag : 0;
     QTTS_TS(1);
@@ -782,9 +837,15 @@ __global__ __launch_bounds__(NW * 64) void skinny8_kernel(const void* kWp, const
 #pragma unroll
         for (int s = 0; s < SPW; ++s) {
             bf16x8 we, wo;
-            *reinterpret_cast<u32x4*>(&we) = wR[i][s][0];
-            if constexpr (FS == 16) *reinterpret_cast<u32x4*>(&wo) = wR[i][s][WPP - 1];
-            else *reinterpret_cast<u32x4*>(&wo) = dpp_ror8(wR[i][s][0]);
+            if constexpr (W8 && FS == 16) {        // one request: codes of the even tile | codes of the odd tile
+                *reinterpret_cast<u32x4*>(&we) = e4m3x8_to_bf16x8(wR[i][s][0][0], wR[i][s][0][1]);
+                *reinterpret_cast<u32x4*>(&wo) = e4m3x8_to_bf16x8(wR[i][s][0][2], wR[i][s][0][3]);
+            } else {
+                const u32x4 w0 = skinny_wa(wR[i][s][0]);
+                *reinterpret_cast<u32x4*>(&we) = w0;
+                if constexpr (FS == 16) *reinterpret_cast<u32x4*>(&wo) = skinny_wa(wR[i][s][WPP - 1]);
+                else *reinterpret_cast<u32x4*>(&wo) = dpp_ror8(w0);
+            }
             acc[s] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(we, xe, acc[s], 0, 0, 0);
             acc[s] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wo, xo, acc[s], 0, 0, 0);
         }
@@ -819,6 +880,7 @@ __global__ __launch_bounds__(NW * 64) void skinny8_kernel(const void* kWp, const
         f32x4 t = red[(0 * NS + s) * 64 + lane];
 #pragma unroll
         for (int w2 = 1; w2 < NW; ++w2) t += red[(w2 * NS + s) * 64 + lane];
+        if constexpr (W8) t = t * scv[s];                        // 2^e[n]: exact, and what the bf16 kernel's sums over d are
         v[s] = t * rstd + (p.bias ? biasv[s] : zero4);
     }
     if constexpr (SPW == 1 && FS == 16) {
@@ -854,6 +916,18 @@ __global__ __launch_bounds__(NW * 64) void skinny8_kernel(const void* kWp, const
     }
     QTTS_TS_DRAINED(5);
     QTTS_TS_END(skinny, 0, p.K, p.N);
+}
+template <int SPW, int FS, int NP, bool NORM, int NW = 8>
+__global__ __launch_bounds__(NW * 64) void skinny8_kernel(const void* kWp, const float* kx, const int* kdone, const float* kres, const float* kbias,
+                                                          int kldx, int kM, int kK, int kldr, SkinnyParams p) {
+    p.Wp = kWp; p.x = kx; p.done_flag = kdone; p.res = kres; p.bias = kbias; p.ldx = kldx; p.M = kM; p.K = kK; p.ldr = kldr;
+    skinny8_body<SPW, FS, NP, NORM, NW, false>(p);
+}
+template <int SPW, int FS, int NP, bool NORM, int NW = 8>
+__global__ __launch_bounds__(NW * 64) void skinny8_fp8_kernel(const void* kWp, const float* kx, const int* kdone, const float* kres, const float* kbias,
+                                                              int kldx, int kM, int kK, int kldr, SkinnyParams p) {
+    p.Wp = kWp; p.x = kx; p.done_flag = kdone; p.res = kres; p.bias = kbias; p.ldx = kldx; p.M = kM; p.K = kK; p.ldr = kldr;
+    skinny8_body<SPW, FS, NP, NORM, NW, true>(p);
 }
 
 // ------------------------------------------------------------------------------------------ fp32 (exact parity mode)
@@ -1188,6 +1262,15 @@ static void launch2_n(const SkinnyParams& p, hipStream_t st) {
     const int grid = p.N / (FS * SPW);
     const size_t lds = (size_t)NW * (SPW * MT + MT) * 64 * 16;
     QTTS_REQUIRE(lds <= 160 * 1024, QTTS_ERR_LIMIT, "skinny: LDS budget exceeded");
+    tl_last_kernel = SKINNY_KERNEL_2 | (p.wfmt == SKINNY_W_FP8 ? SKINNY_KERNEL_FP8 : 0);
+    if constexpr (XB16) {                  // fp8 weights: the same instantiation's fp8 form (launch_skinny has checked that x is bf16)
+        if (p.wfmt == SKINNY_W_FP8) {
+            auto kern8 = skinny2_fp8_kernel<MT, SPW, NW, FS, U, EXACT, NCH>;
+            if (lds > 48 * 1024) ensure_dynamic_lds(reinterpret_cast<const void*>(kern8), 160 * 1024);
+            QTTS_SK_LAUNCH(kern8, dim3(grid), dim3(NW * 64), lds, st, p);
+            return;
+        }
+    }
     auto kern = skinny2_kernel<MT, SPW, NW, FS, XB16, U, EXACT, NCH>;
     if (lds > 48 * 1024) ensure_dynamic_lds(reinterpret_cast<const void*>(kern), 160 * 1024);
     QTTS_SK_LAUNCH(kern, dim3(grid), dim3(NW * 64), lds, st, p);
@@ -1351,6 +1434,12 @@ template <int SPW, int FS, int NP, int NW = 8>
 static void launch8_n(const SkinnyParams& p, hipStream_t st) {
     const int grid = p.N / (FS * SPW);
     const size_t lds = (size_t)NW * (SPW + 1) * 64 * 16;
+    tl_last_kernel = SKINNY_KERNEL_8 | (p.wfmt == SKINNY_W_FP8 ? SKINNY_KERNEL_FP8 : 0);
+    if (p.wfmt == SKINNY_W_FP8) {          // the same instantiation's fp8 form
+        if (p.norm) QTTS_SK_LAUNCH((skinny8_fp8_kernel<SPW, FS, NP, true, NW>), dim3(grid), dim3(NW * 64), lds, st, QTTS_SK8_ARGS(p));
+        else QTTS_SK_LAUNCH((skinny8_fp8_kernel<SPW, FS, NP, false, NW>), dim3(grid), dim3(NW * 64), lds, st, QTTS_SK8_ARGS(p));
+        return;
+    }
     if (p.norm) QTTS_SK_LAUNCH((skinny8_kernel<SPW, FS, NP, true, NW>), dim3(grid), dim3(NW * 64), lds, st, QTTS_SK8_ARGS(p));
     else QTTS_SK_LAUNCH((skinny8_kernel<SPW, FS, NP, false, NW>), dim3(grid), dim3(NW * 64), lds, st, QTTS_SK8_ARGS(p));
 }
@@ -1359,7 +1448,7 @@ static void launch8_n(const SkinnyParams& p, hipStream_t st) {
 // QTTS_SKINNY8_NW = 8 | 4 | 2 | 1 asks for another count where that instantiation exists (A/B; QTTS_ENV).
 template <int SPW, int FS, int NW>
 static bool launch8_nw(const SkinnyParams& p, hipStream_t st) {
-    constexpr int REGS_PER_PAIR = (FS == 16 ? 8 : 4) * SPW + 4;          // operand VGPRs per tile pair
+    constexpr int REGS_PER_PAIR = (FS == 16 ? 8 : 4) * SPW + 4;          // operand VGPRs per tile pair (fp8 weights: half of the first term; the choice stays the bf16 form's)
     switch (p.K / 512) {
 #define QTTS_S8_CASE(KQ)                                                                                         \
         case KQ:                                                                                                 \
@@ -1494,6 +1583,7 @@ static bool launch_skinny8_f32(const SkinnyParams& p, int spw, hipStream_t st) {
 }
 
 void launch_skinny(const SkinnyParams& p, bool bf16, hipStream_t st) {
+    tl_last_kernel = SKINNY_KERNEL_OTHER;
     const int KT = bf16 ? 32 : 16;
     const int fs = p.fs ? p.fs : 16;
     QTTS_REQUIRE(fs == 16 || fs == 8 || fs == 4, QTTS_ERR_ARG, "skinny: fs must be 16, 8 or 4");
@@ -1509,6 +1599,12 @@ void launch_skinny(const SkinnyParams& p, bool bf16, hipStream_t st) {
     QTTS_REQUIRE(!p.out_bf16 || bf16, QTTS_ERR_ARG, "skinny: bf16 output only in bf16 mode");
     QTTS_REQUIRE(bf16 || !p.norm || p.ss_in || skinny_f32_inline_norm(p.M, p.K), QTTS_ERR_ARG,
                  "skinny: the generic fp32 kernel takes the row sums of squares from ss_in");
+    if (p.wfmt) {                        // fp8 weights: skinny8_fp8_kernel (batch <= 8, K % 512 == 0), else skinny2_fp8_kernel; no other kernel reads codes
+        QTTS_REQUIRE(p.wfmt == SKINNY_W_FP8, QTTS_ERR_ARG, "skinny: unknown weight format");
+        QTTS_REQUIRE(bf16 && p.x_bf16, QTTS_ERR_ARG, "skinny: fp8 weights need the bf16 kernel and x as bf16 rows");
+        QTTS_REQUIRE(p.M <= 64, QTTS_ERR_LIMIT, "skinny: fp8 weights are built for M <= 64");
+        QTTS_REQUIRE(p.wscale && !p.ksplit && !p.xp && !p.ks_part && !QTTS_ABL(p, 15), QTTS_ERR_ARG, "skinny: fp8 weights need their row scales and take no split-K / combine / ablation form");
+    }
     if (p.act == ACT_SWIGLU) QTTS_REQUIRE(p.N % 32 == 0 && fs == 16, QTTS_ERR_ARG, "skinny: swiglu needs N % 32 and fs == 16");
     if (p.act == ACT_SWIGLU8) {          // one 16-feature strip = 8 gate + 8 up rows: only the batch <= 8 kernel has this epilogue
         QTTS_REQUIRE(bf16 && fs == 16 && p.x_bf16 && p.M <= 8 && p.K % 512 == 0 && !p.bias && !QTTS_ABL(p, 15), QTTS_ERR_ARG,
@@ -1530,7 +1626,7 @@ void launch_skinny(const SkinnyParams& p, bool bf16, hipStream_t st) {
     }
     const int mt = p.M <= 16 ? 1 : (p.M <= 32 ? 2 : 4);
     if (bf16 && nw == 8 && mt == 1 && launch_skinny8(p, spw, fs, st)) { QTTS_CHECK_HIP(hipGetLastError()); return; }
-    if (bf16 && mt == 2 && launch_skinny_ks(p, fs, st)) { QTTS_CHECK_HIP(hipGetLastError()); return; }
+    if (bf16 && mt == 2 && !p.wfmt && launch_skinny_ks(p, fs, st)) { QTTS_CHECK_HIP(hipGetLastError()); return; }
     if (!bf16 && !QTTS_ABL(p, 15) && launch_skinny8_f32(p, spw, st)) { QTTS_CHECK_HIP(hipGetLastError()); return; }
     if (bf16) {
         if (nw == 8) { if (mt == 1) launch2_mt<1, 8>(p, spw, fs, st); else if (mt == 2) launch2_mt<2, 8>(p, spw, fs, st); else launch2_mt<4, 8>(p, spw, fs, st); }
@@ -1566,6 +1662,79 @@ void pack_skinny_weight(const float* W, int N, int K, bool bf16, void* out_host,
                             float* d = reinterpret_cast<float*>(out_host) + tile * 4;
                             for (int e = 0; e < 4; ++e) d[e] = g ? src[e] * g[k0 + e] : src[e];
                         }
+                    }
+    });
+}
+
+// ------------------------------------------------------------------------------------------ fp8 weights: quantizer and packing (host)
+// RNE to OCP e4m3fn for |v| <= 448 (the caller's scale guarantees it; anything above is clamped to the largest finite code)
+static uint8_t f32_to_e4m3fn(float v) {
+    const uint8_t s = std::signbit(v) ? 0x80 : 0;
+    const float a = std::fabs(v);
+    if (!(a > 0.f)) return s;
+    int q;
+    if (a < 0.015625f) q = (int)std::nearbyint(a * 512.f);               // below 2^-6: multiples of 2^-9 (8 = the smallest normal number)
+    else {
+        int ex;
+        (void)std::frexp(a, &ex);                                        // a = f 2^ex, f in [0.5, 1): the leading bit is 2^(ex - 1)
+        int r = (int)std::nearbyint(std::ldexp(a, 4 - ex));              // 8 .. 16 (both scalings are exact; nearbyint rounds to even)
+        if (r == 16) { r = 8; ++ex; }
+        q = ((ex + 6) << 3) | (r - 8);
+    }
+    return s | (uint8_t)std::min(q, 0x7e);
+}
+static int fp8_row_exponent(float amax) {
+    if (!(amax > 0.f)) return 0;
+    int ex;
+    const float f = std::frexp(amax, &ex);                               // 448 = 0.875 x 2^9: 448 x 2^e >= f x 2^ex, compared exactly
+    const int e = f <= 0.875f ? ex - 9 : ex - 8;
+    return std::max(-100, std::min(100, e));
+}
+void fp8_quantize_rows(const float* W, const float* g, int N, int K, uint8_t* codes, int32_t* exps) {
+    parallel_for(N, [&](int64_t n0, int64_t n1) {
+        for (int64_t n = n0; n < n1; ++n) {
+            const float* w = W + (size_t)n * K;
+            float amax = 0.f;
+            for (int k = 0; k < K; ++k) amax = std::max(amax, std::fabs(g ? w[k] * g[k] : w[k]));
+            const int e = fp8_row_exponent(amax);
+            exps[n] = e;
+            for (int k = 0; k < K; ++k) codes[(size_t)n * K + k] = f32_to_e4m3fn(std::ldexp(g ? w[k] * g[k] : w[k], -e));
+        }
+    });
+}
+void fp8_effective_rows(const float* W, const float* g, int N, int K, float* W_eff) {
+    std::vector<uint8_t> codes((size_t)N * K);
+    std::vector<int32_t> exps((size_t)N);
+    fp8_quantize_rows(W, g, N, K, codes.data(), exps.data());
+    parallel_for(N, [&](int64_t n0, int64_t n1) {
+        for (int64_t n = n0; n < n1; ++n)
+            for (int k = 0; k < K; ++k) {
+                const size_t i = (size_t)n * K + k;
+                const float d = std::ldexp(bf16_to_f32(e4m3_to_bf16_bits(codes[i])), exps[n]);
+                W_eff[i] = !g ? d : (g[k] == 0.f ? W[i] : d / g[k]);
+            }
+    });
+}
+size_t skinny_fp8_code_bytes(int N, int K, int fs) {
+    const int nkt = K / 32;
+    return (size_t)N * 32 * (fs == 16 ? ((nkt + 1) / 2) * 2 : nkt);
+}
+void pack_skinny_weight_fp8(const float* W, int N, int K, void* codes_out, float* scales_out, const float* g, int fs) {
+    const int nkt = K / 32, strips = N / fs, npairs = (nkt + 1) / 2;
+    std::vector<uint8_t> codes((size_t)N * K);
+    std::vector<int32_t> exps((size_t)N);
+    fp8_quantize_rows(W, g, N, K, codes.data(), exps.data());
+    for (int n = 0; n < N; ++n) scales_out[n] = std::ldexp(1.f, exps[n]);
+    uint8_t* out = reinterpret_cast<uint8_t*>(codes_out);
+    memset(out, 0, skinny_fp8_code_bytes(N, K, fs));
+    parallel_for(strips, [&](int64_t s0, int64_t s1) {
+        for (int64_t s = s0; s < s1; ++s)
+            for (int kt = 0; kt < nkt; ++kt)
+                for (int q = 0; q < 4; ++q)
+                    for (int i = 0; i < fs; ++i) {
+                        const size_t dst = fs == 16 ? ((((size_t)s * npairs + (kt >> 1)) * 64 + q * 16 + i) * 2 + (kt & 1)) * 8
+                                                    : (((size_t)s * nkt + kt) * (fs * 4) + q * fs + i) * 8;
+                        memcpy(out + dst, &codes[(size_t)(s * fs + i) * K + kt * 32 + q * 8], 8);
                     }
     });
 }

@@ -33,6 +33,8 @@ struct LayerW {
     DevBuf o_p16;                     // o-projection in 16-feature strips for the fused attention + o-projection launch (code predictor, bf16 only)
     DevBuf gu_mlp, d_p16;             // the fused MLP launch's operators (cp_mlp.hip: gate|up by workgroup, down in 16-feature strips; code predictor, bf16 only)
     DevBuf qkv_r, o_r, gu_r, d_r;     // row-major (prefill, talker only)
+    bool w8 = false;                  // fp8 weights (talker layers of an engine with weight_format fp8): the five packed operators hold e4m3fn codes, ...
+    DevBuf qkv_s, o_s, gu_s, gu8_s, d_s;   // ... and these their rows' power-of-two scales
     DevBuf g1, g2, qn, kn;
 };
 struct StackDims { int H, I, nh, nkv, hd, qd, kvd; float eps; };
@@ -59,6 +61,10 @@ struct qtts_talker {
     DevBuf emb_text, tp_in, err_flag;          // text embedding table (prompt assembly), gathered rows, device error flag
     int64_t text_vocab = 0;
     double weight_bytes_frame = 0;
+    // fp8 weights (qtts_talker_set_weight_format, before finalize): the talker layers' decode operators as e4m3fn codes + row scales.  The
+    // engine is then the bf16 engine of the checkpoint W_eff (skinny.hip: fp8_effective_rows), bit for bit.
+    int weight_format = QTTS_WEIGHTS_DEFAULT;
+    int64_t packed_bytes = 0;           // bytes of every packed decode operator uploaded at finalize
 
     // KV caches
     DevBuf kpool_t, vpool_t, kpool_c, vpool_c, ptab_t, ptab_c, attn_part;
@@ -232,6 +238,22 @@ struct qtts_talker {
         std::vector<char> h(skinny_packed_bytes(N, K, bf16));
         pack_skinny_weight(w.data(), N, K, bf16, h.data(), g ? g->data() : nullptr, fs);     // g: folded RMSNorm weight
         d.upload(h.data(), h.size());
+        packed_bytes += (int64_t)h.size();
+    }
+    // the same operator as fp8 codes (the strip width's layout) + one scale per packed row
+    void upload_packed_fp8(DevBuf& d, DevBuf& sc, const std::vector<float>& w, int N, int K, const std::vector<float>* g = nullptr, int fs = 16) {
+        std::vector<char> h(skinny_fp8_code_bytes(N, K, fs));
+        std::vector<float> s((size_t)N);
+        pack_skinny_weight_fp8(w.data(), N, K, h.data(), s.data(), g ? g->data() : nullptr, fs);
+        d.upload(h.data(), h.size());
+        sc.upload(s.data(), s.size() * 4);
+        packed_bytes += (int64_t)h.size() + (int64_t)s.size() * 4;
+    }
+    // W_eff of a row-major operator: what the bf16 engine must be bound with to pack exactly the fp8 engine's d
+    static std::vector<float> effective_rows(const std::vector<float>& w, int N, int K, const std::vector<float>* g) {
+        std::vector<float> e(w.size());
+        fp8_effective_rows(w.data(), g ? g->data() : nullptr, N, K, e.data());
+        return e;
     }
     // Narrow strips when the GEMM would otherwise launch too few workgroups to pull its weights (bf16 kernel only).  Every
     // workgroup re-reads the whole x (M x K bf16) through its XCD's L2, so MORE workgroups also cost more (round-2 sweep,
@@ -317,17 +339,25 @@ struct qtts_talker {
         auto guw = interleave_gu(PS(p + "mlp.gate_proj.weight", {d.I, d.H}), PS(p + "mlp.up_proj.weight", {d.I, d.H}), d.I, d.H);
         auto& ow = PS(p + "self_attn.o_proj.weight", {d.H, d.qd});
         auto& dw = PS(p + "mlp.down_proj.weight", {d.H, d.I});
-        upload_packed(L.qkv_p, qkvw, d.qd + 2 * d.kvd, d.H, &PS(p + "input_layernorm.weight", {d.H}));
+        const auto& g1 = PS(p + "input_layernorm.weight", {d.H});
+        const auto& g2 = PS(p + "post_attention_layernorm.weight", {d.H});
+        // fp8 weights: the talker stack's decode operators as codes + row scales (strip widths chosen as for bf16, on the bf16 byte count);
+        // everything else of the layer, and every operator of the code predictor, as before
+        L.w8 = rows && weight_format == QTTS_WEIGHTS_FP8;
+        auto packed = [&](DevBuf& dst, DevBuf& sc, const std::vector<float>& w, int N, int K, const std::vector<float>* g, int fs) {
+            if (L.w8) upload_packed_fp8(dst, sc, w, N, K, g, fs); else upload_packed(dst, w, N, K, g, fs);
+        };
+        packed(L.qkv_p, L.qkv_s, qkvw, d.qd + 2 * d.kvd, d.H, &g1, 16);
         L.fs_o = choose_fs(d.H, d.qd); L.fs_d = choose_fs(d.H, d.I);
-        upload_packed(L.o_p, ow, d.H, d.qd, nullptr, L.fs_o);
-        upload_packed(L.gu_p, guw, 2 * d.I, d.H, &PS(p + "post_attention_layernorm.weight", {d.H}));
+        packed(L.o_p, L.o_s, ow, d.H, d.qd, nullptr, L.fs_o);
+        packed(L.gu_p, L.gu_s, guw, 2 * d.I, d.H, &g2, 16);
         // (only engines that can run at batch <= 8 at all pay for the second copy -- 1.46 GB at 1.7B dims; an engine created for waves
         // of 9..32 rows keeps the strip-pair kernel for a short last wave: ADVICE r3; an engine created for 33..64 rows follows the live batch
         // of every call and runs a call of <= 8 rows exactly as an engine created for 8 does)
         if (bf16 && swiglu8_env && (cfg.max_batch <= 8 || cfg.max_batch > 32) && d.I % 8 == 0 && skinny_swiglu8_takes(d.H))
-            upload_packed(L.gu_p8, interleave_gu8(PS(p + "mlp.gate_proj.weight", {d.I, d.H}), PS(p + "mlp.up_proj.weight", {d.I, d.H}), d.I, d.H),
-                          2 * d.I, d.H, &PS(p + "post_attention_layernorm.weight", {d.H}));
-        upload_packed(L.d_p, dw, d.H, d.I, nullptr, L.fs_d);
+            packed(L.gu_p8, L.gu8_s, interleave_gu8(PS(p + "mlp.gate_proj.weight", {d.I, d.H}), PS(p + "mlp.up_proj.weight", {d.I, d.H}), d.I, d.H),
+                   2 * d.I, d.H, &g2, 16);
+        packed(L.d_p, L.d_s, dw, d.H, d.I, nullptr, L.fs_d);
         // code predictor, bf16: passes >= 1 run attention + o-projection as ONE launch (attention.hip: cp_attn_o_kernel), whose waves own
         // 16-feature strips of the operator (a second packed copy: 4 MB per layer)
         if (bf16 && !rows && cp_attn_o_env && d.nh == 16 && d.nkv == 8 && d.hd == 128 && d.H % 128 == 0)
@@ -337,18 +367,25 @@ struct qtts_talker {
         if (!rows && ((cp_mlp_env && cp_mlp_instantiated(d.H, d.I, bf16)) || (cp_mlp32_env && bf16 && cp_mlp32_instantiated(d.H, d.I)))) {
             std::vector<char> h(cp_mlp_gu_bytes(d.H, d.I, bf16));
             pack_cp_mlp_gu(PS(p + "mlp.gate_proj.weight", {d.I, d.H}).data(), PS(p + "mlp.up_proj.weight", {d.I, d.H}).data(),
-                           PS(p + "post_attention_layernorm.weight", {d.H}).data(), d.H, d.I, bf16, h.data());
+                           g2.data(), d.H, d.I, bf16, h.data());
             L.gu_mlp.upload(h.data(), h.size());
             if (bf16) upload_packed(L.d_p16, dw, d.H, d.I, nullptr, 16);
         }
-        if (rows) {
+        if (rows && L.w8) {
+            // the prompt must see the same model: the row-major prefill copies come from W_eff (rows are quantized one by one, so the
+            // interleaved gate|up image is the interleave of the two W_eff)
+            upload_rows(L.qkv_r, effective_rows(qkvw, d.qd + 2 * d.kvd, d.H, &g1));
+            upload_rows(L.o_r, effective_rows(ow, d.H, d.qd, nullptr));
+            upload_rows(L.gu_r, effective_rows(guw, 2 * d.I, d.H, &g2));
+            upload_rows(L.d_r, effective_rows(dw, d.H, d.I, nullptr));
+        } else if (rows) {
             upload_rows(L.qkv_r, qkvw);
             upload_rows(L.o_r, ow);
             upload_rows(L.gu_r, guw);
             upload_rows(L.d_r, dw);
         }
-        upload_f(L.g1, PS(p + "input_layernorm.weight", {d.H}));
-        upload_f(L.g2, PS(p + "post_attention_layernorm.weight", {d.H}));
+        upload_f(L.g1, g1);
+        upload_f(L.g2, g2);
         upload_f(L.qn, PS(p + "self_attn.q_norm.weight", {d.hd}));
         upload_f(L.kn, PS(p + "self_attn.k_norm.weight", {d.hd}));
     }
@@ -358,7 +395,7 @@ struct qtts_talker {
 
     void skinny(const SkinnyParams& p, hipStream_t st) {
         if (timing_now) {
-            LaunchEv e{nullptr, nullptr, cur_stack, p.N, p.K, 0.0};
+            LaunchEv e{nullptr, nullptr, cur_stack, p.N, p.K, p.wfmt ? (double)p.N * p.K + 4.0 * p.N : 0.0};     // (fp8: codes + row scales)
             QTTS_CHECK_HIP(hipEventCreate(&e.a)); QTTS_CHECK_HIP(hipEventCreate(&e.b));
             ev.push_back(e);
             skinny_set_launch_events(e.a, e.b);
@@ -401,6 +438,7 @@ struct qtts_talker {
     int ks_split_per_step = 0;
     int ks_mink = QTTS_OPT_INT("QTTS_SKINNY_KS_MINK", 6144);
     void ks_arm(SkinnyParams& q, int slot) {
+        if (q.wfmt) return;                // (an fp8 operator keeps skinny2_fp8_kernel: the split-K kernel reads bf16 tiles)
         if (!ks_split_env || !ks_part.p || !bf16 || q.M <= 16 || q.M > 32 || slot < 0 || slot >= 256 || skinny_only) return;
         if (q.K < ks_mink || !skinny_ksplit_takes(q.M, q.N, q.K, q.fs ? q.fs : 16)) return;
         q.ks_part = ks_part.as<float>(); q.ks_part_bytes = ks_part.bytes; q.ks_serial = ss.frame_serial; q.ks_slot = slot; q.ks_pause = ks_pause;
@@ -425,6 +463,7 @@ struct qtts_talker {
         p.done_flag = ss.done;
         p.x = xs; p.ldx = d.H; p.M = M; p.Wp = L.qkv_p.p; p.N = d.qd + 2 * d.kvd; p.K = d.H;
         p.out = qkvb; p.ldo = d.qd + 2 * d.kvd; p.act = ACT_NONE;
+        if (L.w8) { p.wfmt = SKINNY_W_FP8; p.wscale = L.qkv_s.as<float>(); }
         AttnDecodeParams a{};
         a.qkv = qkvb; a.ld = d.qd + 2 * d.kvd; a.B = B; a.n_new = n_new; a.nh = d.nh; a.nkv = d.nkv; a.hd = d.hd;
         a.qw = L.qn.as<float>(); a.kw = L.kn.as<float>(); a.eps = d.eps; a.inv_freq = inv_freq; a.n_pad = npad;
@@ -517,6 +556,7 @@ struct qtts_talker {
         o.x_bf16 = att16;
         o.x = attb; o.ldx = d.qd; o.M = M; o.Wp = L.o_p.p; o.N = d.H; o.K = d.qd; o.res = xs; o.ldr = d.H;
         o.out = xs; o.ldo = d.H; o.act = ACT_NONE; o.out16 = h16 ? xs16 : nullptr; o.fs = L.fs_o;
+        if (L.w8) { o.wfmt = SKINNY_W_FP8; o.wscale = L.o_s.as<float>(); }
         if (splitk) { o.out = sk_part.as<float>(); o.ksplit = 2; o.part_stride = pstride; }     // (o.res = xs: half 0 = residual + its sums)
         const int ks_slot0 = len_dev ? 2 * layer : 2 * (int)tl.size() + 2 * (len_static * (int)cl.size() + layer);
         if (n_new == 1) ks_arm(o, ks_slot0);
@@ -561,13 +601,15 @@ struct qtts_talker {
         g.out_bf16 = act16;
         if (splitk) { g.xp = sk_part.as<float>(); g.xp_stride = pstride; g.x_out = xs; }     // (residual + half 0) + half 1 of the o-projection
         norm_input(g, d, h16 ? xs16 : nullptr, st);
-        if (L.gu_p8.p && g.x_bf16 && M <= 8 && !skinny_ablate_or_off()) { g.Wp = L.gu_p8.p; g.act = ACT_SWIGLU8; }
+        if (L.w8) { g.wfmt = SKINNY_W_FP8; g.wscale = L.gu_s.as<float>(); }
+        if (L.gu_p8.p && g.x_bf16 && M <= 8 && !skinny_ablate_or_off()) { g.Wp = L.gu_p8.p; g.act = ACT_SWIGLU8; if (L.w8) g.wscale = L.gu8_s.as<float>(); }
         skinny(g, st);
         SkinnyParams dn{};
         dn.done_flag = ss.done;
         dn.x_bf16 = act16;
         dn.x = actb; dn.ldx = d.I; dn.M = M; dn.Wp = L.d_p.p; dn.N = d.H; dn.K = d.I; dn.res = xs; dn.ldr = d.H;
         dn.out = xs; dn.ldo = d.H; dn.act = ACT_NONE; dn.out16 = h16 ? xs16 : nullptr; dn.fs = L.fs_d;
+        if (L.w8) { dn.wfmt = SKINNY_W_FP8; dn.wscale = L.d_s.as<float>(); }
         if (splitk && !last_layer) { dn.out = sk_part.as<float>(); dn.ksplit = 2; dn.part_stride = pstride; sk_pending = true; }   // (dn.res = xs)
         if (n_new == 1) ks_arm(dn, (len_dev ? 2 * layer : 2 * (int)tl.size() + 2 * (len_static * (int)cl.size() + layer)) + 1);
         skinny(dn, st);
@@ -973,6 +1015,8 @@ void qtts_talker::finalize() {
     weight_bytes_frame = c.num_hidden_layers * layer_b(td) + eb * (double)c.vocab_size * td.H +
                          (G - 1) * (c.cp_num_hidden_layers * layer_b(cd) + eb * (double)c.cp_vocab_size * cd.H +
                                     (has_proj ? eb * (double)cd.H * td.H : 0.0));
+    if (weight_format == QTTS_WEIGHTS_FP8)      // the talker layers' operators stream N K + 4 N bytes each
+        weight_bytes_frame -= c.num_hidden_layers * (layer_b(td) * 0.5 - 4.0 * ((double)(td.qd + 2 * td.kvd) + 2.0 * td.H + 2.0 * td.I));
     if (has_proj && G > 2) weight_bytes_frame -= (G - 2) * eb * (double)cd.H * td.H;   // only pass 0 still runs the projection
     if (G > 2) weight_bytes_frame -= (G - 2) * eb * (double)(cd.qd + 2 * cd.kvd) * cd.H;   // layer-0 qkv GEMM of passes >= 1
 
@@ -2074,6 +2118,91 @@ int qtts_talker_set_kv_pool(qtts_talker* t, int32_t n_pages) {
     if (n_pages != 0 && n_pages < one_row)
         throw Error(QTTS_ERR_LIMIT, "set_kv_pool: " + std::to_string(n_pages) + " pages do not hold one request of max_seq keys (" + std::to_string(one_row) + " pages)");
     t->pool_pages = n_pages;
+    QTTS_API_END
+}
+
+int qtts_talker_set_weight_format(qtts_talker* t, int32_t fmt) {
+    QTTS_API_BEGIN
+    QTTS_REQUIRE(t, QTTS_ERR_ARG, "null handle");
+    QTTS_REQUIRE(!t->finalized, QTTS_ERR_STATE, "set_weight_format after finalize");
+    QTTS_REQUIRE(fmt == QTTS_WEIGHTS_DEFAULT || fmt == QTTS_WEIGHTS_FP8, QTTS_ERR_ARG, "set_weight_format: unknown format " + std::to_string(fmt) + " (0 default, 1 fp8)");
+    QTTS_REQUIRE(fmt == QTTS_WEIGHTS_DEFAULT || t->bf16, QTTS_ERR_ARG, "set_weight_format: fp8 weights need a bf16 engine (the fp32 engine is the exact parity mode)");
+    t->weight_format = fmt;
+    QTTS_API_END
+}
+
+int qtts_talker_weight_format(qtts_talker* t, int32_t* fmt_host, int64_t* packed_bytes_host) {
+    QTTS_API_BEGIN
+    QTTS_REQUIRE(t, QTTS_ERR_ARG, "null handle");
+    if (fmt_host) *fmt_host = t->weight_format;
+    if (packed_bytes_host) *packed_bytes_host = t->packed_bytes;
+    QTTS_API_END
+}
+
+int qtts_fp8_quantize_rows(const float* W, const float* g_or_null, int32_t N, int32_t K, uint8_t* codes, int32_t* exps) {
+    QTTS_API_BEGIN
+    QTTS_REQUIRE(W && codes && exps && N >= 1 && K >= 1, QTTS_ERR_ARG, "fp8_quantize_rows: null argument or empty shape");
+    fp8_quantize_rows(W, g_or_null, N, K, codes, exps);
+    QTTS_API_END
+}
+
+int qtts_fp8_effective_rows(const float* W, const float* g_or_null, int32_t N, int32_t K, float* W_eff) {
+    QTTS_API_BEGIN
+    QTTS_REQUIRE(W && W_eff && N >= 1 && K >= 1, QTTS_ERR_ARG, "fp8_effective_rows: null argument or empty shape");
+    fp8_effective_rows(W, g_or_null, N, K, W_eff);
+    QTTS_API_END
+}
+
+int qtts_debug_last_decode_gemm_kernel(int32_t* kind_host) {
+    QTTS_API_BEGIN
+    QTTS_REQUIRE(kind_host, QTTS_ERR_ARG, "null argument");
+    *kind_host = skinny_last_kernel();
+    QTTS_API_END
+}
+
+// TEST HOOK: one launch_skinny call on host operands, bf16 or fp8 weights (include/qtts.h)
+int qtts_debug_decode_gemm(const float* x, const float* W, const float* g_or_null, const float* bias_or_null, const float* res_or_null,
+                           int32_t M, int32_t N, int32_t K, int32_t fs, int32_t norm, int32_t act, int32_t fmt, int32_t ldo,
+                           float* out, uint16_t* out16_or_null) {
+    QTTS_API_BEGIN
+    QTTS_REQUIRE(x && W && out, QTTS_ERR_ARG, "debug_decode_gemm: null argument");
+    QTTS_REQUIRE(M >= 1 && M <= 64 && N >= 16 && K >= 32 && K % 32 == 0, QTTS_ERR_ARG, "debug_decode_gemm: 1 <= M <= 64, N >= 16, K % 32 == 0");
+    QTTS_REQUIRE(fs == 16 || fs == 8 || fs == 4, QTTS_ERR_ARG, "debug_decode_gemm: fs must be 16, 8 or 4");
+    QTTS_REQUIRE(N % fs == 0, QTTS_ERR_ARG, "debug_decode_gemm: N % fs");
+    QTTS_REQUIRE(fmt == QTTS_WEIGHTS_DEFAULT || fmt == QTTS_WEIGHTS_FP8, QTTS_ERR_ARG, "debug_decode_gemm: unknown weight format");
+    const bool glu = act == ACT_SWIGLU || act == ACT_SWIGLU8;
+    QTTS_REQUIRE(act == ACT_NONE || glu, QTTS_ERR_ARG, "debug_decode_gemm: act 0, 2 (SwiGLU strip pairs) or 5 (SwiGLU of one strip)");
+    const int No = glu ? N / 2 : N;
+    QTTS_REQUIRE(ldo >= No && ldo % 4 == 0, QTTS_ERR_ARG, "debug_decode_gemm: ldo >= output columns, ldo % 4 == 0");
+    DevBuf Wd, sd, xd, od, o16d, rd, bd;
+    if (fmt == QTTS_WEIGHTS_FP8) {
+        std::vector<char> h(skinny_fp8_code_bytes(N, K, fs));
+        std::vector<float> s((size_t)N);
+        pack_skinny_weight_fp8(W, N, K, h.data(), s.data(), g_or_null, fs);
+        Wd.upload(h.data(), h.size());
+        sd.upload(s.data(), s.size() * 4);
+    } else {
+        std::vector<char> h(skinny_packed_bytes(N, K, true));
+        pack_skinny_weight(W, N, K, true, h.data(), g_or_null, fs);
+        Wd.upload(h.data(), h.size());
+    }
+    std::vector<bf16_t> x16((size_t)M * K);
+    for (size_t i = 0; i < x16.size(); ++i) x16[i] = f32_to_bf16(x[i]);
+    xd.upload(x16.data(), x16.size() * 2);
+    od.upload(out, (size_t)M * ldo * 4);
+    if (out16_or_null) o16d.upload(out16_or_null, (size_t)M * ldo * 2);
+    if (res_or_null) rd.upload(res_or_null, (size_t)M * ldo * 4);
+    if (bias_or_null) bd.upload(bias_or_null, (size_t)N * 4);
+    SkinnyParams p{};
+    p.x = xd.as<float>(); p.x_bf16 = 1; p.ldx = K; p.M = M; p.Wp = Wd.p; p.N = N; p.K = K; p.fs = fs; p.norm = norm ? 1 : 0; p.eps = 1e-6f;
+    p.bias = bias_or_null ? bd.as<float>() : nullptr;
+    if (res_or_null) { p.res = rd.as<float>(); p.ldr = ldo; }
+    p.out = od.as<float>(); p.ldo = ldo; p.out16 = out16_or_null ? o16d.p : nullptr; p.act = act;
+    if (fmt == QTTS_WEIGHTS_FP8) { p.wfmt = SKINNY_W_FP8; p.wscale = sd.as<float>(); }
+    launch_skinny(p, true, nullptr);
+    QTTS_CHECK_HIP(hipDeviceSynchronize());
+    QTTS_CHECK_HIP(hipMemcpy(out, od.p, (size_t)M * ldo * 4, hipMemcpyDeviceToHost));
+    if (out16_or_null) QTTS_CHECK_HIP(hipMemcpy(out16_or_null, o16d.p, (size_t)M * ldo * 2, hipMemcpyDeviceToHost));
     QTTS_API_END
 }
 

@@ -179,16 +179,17 @@ class Qwen3TTSForConditionalGeneration:
 
     def __init__(self, config: Any, state_dict: Dict[str, torch.Tensor], device: str = "cuda:0",
                  dtype: torch.dtype = torch.bfloat16, max_batch: int = 8, max_seq: int = 4096,
-                 use_graph: bool = True, kv_pages: Optional[int] = None):
+                 use_graph: bool = True, kv_pages: Optional[int] = None, weight_format: Optional[str] = None):
         """`kv_pages`: the talker's KV cache as a shared pool of that many 16-key pages (`TalkerEngine(kv_pages=...)`); None: the static
-        max_batch x max_seq layout."""
+        max_batch x max_seq layout.  `weight_format`: None or "fp8" (`TalkerEngine(weight_format=...)`: the talker layers' decode operators
+        as e4m3 codes, opt-in; the prompt-side tables and everything else are unchanged)."""
         self.config = TalkerConfig.from_any(config)
         self.dtype = dtype
         sd = state_dict
         if any(k.startswith("talker.") for k in sd):
             sd = {k[len("talker."):]: v for k, v in sd.items() if k.startswith("talker.")}
         self.talker = TalkerEngine(self.config, sd, weight_dtype=dtype, device=device, max_batch=max_batch,
-                                   max_seq=max_seq, use_graph=use_graph, kv_pages=kv_pages)
+                                   max_seq=max_seq, use_graph=use_graph, kv_pages=kv_pages, weight_format=weight_format)
         self.device = self.talker.device            # (the HIP device the engine accepted: `_lib.hip_device` refuses anything else)
         if "model.text_embedding.weight" not in sd:
             raise KeyError("state_dict has no talker.model.text_embedding.weight (needed by the prompt assembly)")
@@ -468,7 +469,8 @@ class Qwen3TTSModel:
     def from_pretrained(cls, pretrained_model_name_or_path: str, **kwargs) -> "Qwen3TTSModel":
         """Same kwargs as the reference (qwen3_tts_model.py:82-121): `device_map`, `dtype`,
         `attn_implementation` (accepted; the HIP engine has one attention path).  `kv_pages`: the talker's KV cache as a shared page
-        pool of that size (`TalkerEngine(kv_pages=...)`; `TalkerEngine.kv_page_bytes` per page); None: max_batch x max_seq keys."""
+        pool of that size (`TalkerEngine(kv_pages=...)`; `TalkerEngine.kv_page_bytes` per page); None: max_batch x max_seq keys.
+        `weight_format="fp8"`: the talker layers' decode operators as e4m3 codes (`TalkerEngine(weight_format=...)`, opt-in)."""
         from safetensors.torch import load_file
         from .codec import Qwen3TTSTokenizer
         path = resolve_checkpoint_dir(pretrained_model_name_or_path, **kwargs)
@@ -493,7 +495,7 @@ class Qwen3TTSModel:
             max_seq = min(16384, ((want + 1024 + 255) // 256) * 256)
         model = Qwen3TTSForConditionalGeneration(cfg, sd, device=device, dtype=dtype,
                                                  max_batch=kwargs.get("max_batch", 8), max_seq=int(max_seq),
-                                                 kv_pages=kwargs.get("kv_pages"))
+                                                 kv_pages=kwargs.get("kv_pages"), weight_format=kwargs.get("weight_format"))
         st_dir = os.path.join(path, "speech_tokenizer")                       # M:1900-1920
         if os.path.isdir(st_dir):
             model.load_speech_tokenizer(Qwen3TTSTokenizer.from_pretrained(st_dir, device_map=device, dtype=dtype,

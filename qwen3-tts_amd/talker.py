@@ -340,8 +340,12 @@ class TalkerEngine:
 
     def __init__(self, config: Any, state_dict: Dict[str, torch.Tensor], weight_dtype: torch.dtype = torch.bfloat16,
                  device: str = "cuda:0", max_batch: int = 8, max_seq: int = 4096, use_graph: bool = True, shared_device: bool = False,
-                 kv_pages: Optional[int] = None):
-        """`kv_pages`: the talker's KV cache as a shared pool of that many 16-key pages (`kv_page_bytes` each) instead of `max_batch` x
+                 kv_pages: Optional[int] = None, weight_format: Optional[str] = None):
+        """`weight_format`: None (the engine as it is) or "fp8": the talker layers' decode operators as e4m3 codes with a power-of-two scale
+        per output row -- half the bytes per frame for them (bf16 engines only; include/qtts.h `qtts_talker_set_weight_format`).  The engine
+        is then, bit for bit, the bf16 engine of `fp8.effective_state_dict(config, state_dict)`; `packed_weight_bytes` says what it holds.
+
+        `kv_pages`: the talker's KV cache as a shared pool of that many 16-key pages (`kv_page_bytes` each) instead of `max_batch` x
         `max_seq` keys reserved per row (include/qtts.h `qtts_talker_set_kv_pool`); at least ceil(max_seq / 16).  A continuous stream then
         takes pages as its rows grow and `generate(schedule="continuous")` preempts by restart when the pool runs dry (`_refill_stream`);
         every other call reserves its worst case when it begins.  None: the static layout.
@@ -356,6 +360,11 @@ class TalkerEngine:
         self.weight_dtype = weight_dtype
         self.max_batch, self.max_seq = int(max_batch), int(max_seq)
         self.kv_pages = int(kv_pages) if kv_pages else None
+        if weight_format not in (None, "fp8"):
+            raise ValueError(f"weight_format must be None or 'fp8', not {weight_format!r}")
+        if weight_format == "fp8" and weight_dtype != torch.bfloat16:
+            raise ValueError("weight_format='fp8' needs a bf16 engine (weight_dtype=torch.bfloat16); the fp32 engine is the exact parity mode")
+        self.weight_format = weight_format
         self._lib = _lib.load_library()
         self._lock = threading.RLock()
         c = self.config
@@ -375,6 +384,8 @@ class TalkerEngine:
             _lib.check(self._lib.qtts_talker_create(C.byref(tc), C.byref(self._h)))
             if self.kv_pages:
                 _lib.check(self._lib.qtts_talker_set_kv_pool(self._h, self.kv_pages))
+            if self.weight_format == "fp8":
+                _lib.check(self._lib.qtts_talker_set_weight_format(self._h, _lib.WEIGHTS_FP8))
             has_prefix = any(k.startswith("talker.") for k in state_dict)
             for name, t in state_dict.items():
                 if has_prefix:
@@ -406,6 +417,13 @@ class TalkerEngine:
         (1.7B dims in bf16: 28 x 2 x 8 x 16 x 128 x 2 B = 1.835 MB)."""
         c = self.config
         return int(c.num_hidden_layers) * 2 * int(c.num_key_value_heads) * 16 * int(c.head_dim) * (2 if self.weight_dtype == torch.bfloat16 else 4)
+
+    @property
+    def packed_weight_bytes(self) -> int:
+        """Bytes of every packed decode operator the engine holds on the device (an fp8 operator: N K + 4 N; its bf16 form: 2 N K)."""
+        n = C.c_int64(0)
+        _lib.check(self._lib.qtts_talker_weight_format(self._h, None, C.byref(n)))
+        return int(n.value)
 
     @_lib.locked
     def set_profile(self, enable):
