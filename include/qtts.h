@@ -693,12 +693,20 @@ int qtts_fp8_effective_rows(const float* W /* (N, K) */, const float* g_or_null 
  *   strip, as bf16 (fmt 0) or as fp8 codes + scales (fmt QTTS_WEIGHTS_FP8).  W is given in PACKED row order (the caller interleaves
  *   gate / up rows for act 2 = SwiGLU strip pairs, 5 = SwiGLU of one strip).  No = N / 2 with a SwiGLU act, else N; out / res / out16
  *   have leading dimension ldo >= No (columns beyond No are never written); out16 (bf16 bits, NULL = none) is the kernel's bf16 shadow.
- *   last_decode_gemm_kernel: the kernel family that call ran on the calling thread: 2 skinny2_kernel, 8 skinny8_kernel (the batch <= 8 form),
- *   + 16 for their fp8 forms, 0 any other. */
+ *   last_decode_gemm_kernel: the kernel family that call ran on the calling thread: 2 skinny2_kernel, 4 skinny2_ks_kernel (split-K, batch
+ *   17..32), 8 skinny8_kernel (the batch <= 8 form), + 16 for their fp8 forms, 0 any other.
+ *   decode_gemm_ks: the same call with what the split-K form needs (plain GEMM: no norm, no act; 17 <= M <= 32 splits where the launcher
+ *   has an instantiation and QTTS_SKINNY_KS / QTTS_SKINNY_KS_MINK allow, any other shape runs as in decode_gemm): an 8 MB granule
+ *   workspace filled with 0xFF, the device word `serial` the tags derive from, and `launches` >= 1 back-to-back launches with slots
+ *   3 + 7 l on that one workspace (each rewrites out).  out / out16 have M + 1 rows: row M is a guard the kernel must not write.
+ *   QTTS_ERR_STATE if a reducer gave up (error or latch word raised). */
 int qtts_debug_last_decode_gemm_kernel(int32_t* kind_host);
 int qtts_debug_decode_gemm(const float* x /* (M, K) */, const float* W /* (N, K) */, const float* g_or_null, const float* bias_or_null /* (N) */,
                            const float* res_or_null /* (M, ldo) */, int32_t M, int32_t N, int32_t K, int32_t fs, int32_t norm, int32_t act,
                            int32_t fmt, int32_t ldo, float* out /* (M, ldo) in/out */, uint16_t* out16_or_null /* (M, ldo) in/out */);
+int qtts_debug_decode_gemm_ks(const float* x /* (M, K) */, const float* W /* (N, K) */, const float* g_or_null, const float* bias_or_null /* (N) */,
+                              const float* res_or_null /* (M, ldo) */, int32_t M, int32_t N, int32_t K, int32_t fs, int32_t fmt, int32_t ldo,
+                              float* out /* (M + 1, ldo) in/out */, uint16_t* out16_or_null /* (M + 1, ldo) in/out */, int32_t launches, int32_t serial);
 
 /* Test/diagnostic hooks (device -> caller device buffers, after prefill / a generate call). */
 int qtts_talker_debug_logits(qtts_talker* t, float* logits_dev /* (B, vocab) */, void* stream);

@@ -134,7 +134,7 @@ SYMBOLS = ["qtts_last_error", "qtts_abi_version", "qtts_set_option", "qtts_get_o
            "qtts_talker_stream_begin_admitting_rows", "qtts_talker_stream_row_lens", "qtts_talker_stream_mode",
            "qtts_talker_set_kv_pool", "qtts_talker_stream_kv", "qtts_talker_stream_evict",
            "qtts_talker_set_row_warpers", "qtts_talker_sampler_class", "qtts_talker_set_row_processors",
-           "qtts_talker_set_weight_format", "qtts_talker_weight_format", "qtts_debug_decode_gemm", "qtts_debug_last_decode_gemm_kernel",
+           "qtts_talker_set_weight_format", "qtts_talker_weight_format", "qtts_debug_decode_gemm", "qtts_debug_decode_gemm_ks", "qtts_debug_last_decode_gemm_kernel",
            "qtts_talker_debug_logits", "qtts_talker_debug_kv_table", "qtts_talker_debug_cp_logits", "qtts_talker_get_stats", "qtts_talker_get_gemm_profile", "qtts_talker_set_teacher",
            "qtts_talker_set_profile"]
 
@@ -246,6 +246,7 @@ def load_library():
     lib.qtts_fp8_effective_rows.argtypes = [vp, vp, i32, i32, vp]
     lib.qtts_debug_last_decode_gemm_kernel.argtypes = [C.POINTER(C.c_int32)]
     lib.qtts_debug_decode_gemm.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp]
+    lib.qtts_debug_decode_gemm_ks.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, i32]
     lib.qtts_talker_set_row_warpers.argtypes = [vp, C.POINTER(RowWarpersC), i32]
     lib.qtts_talker_set_row_processors.argtypes = [vp, C.POINTER(RowProcessorsC), i32]
     lib.qtts_talker_sampler_class.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]

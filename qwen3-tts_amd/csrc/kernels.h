@@ -83,7 +83,7 @@ struct SkinnyParams {
     const float* xp;             // consumer: x is formed as xp[0] + xp[1] (= residual + half 0, half 1), at xp and xp + xp_stride, [M][ldx]; `x` is not read
     size_t xp_stride;
     float* x_out;                //    ... and workgroup 0 writes the combined rows here (outside the halves)
-    // bf16, batch 17..32, plain GEMM without norm (round 6: skinny2_ks_kernel): K split over the workgroups of a 32-feature strip group, the
+    // bf16 or fp8 weights, batch 17..32, plain GEMM without norm (round 6: skinny2_ks_kernel / skinny2_ks_fp8_kernel): K split over the workgroups of a 32-feature strip group, the
     // partial sums handed to the group's LAST workgroup as tagged granules (granule.h) and added there in k order
     float* ks_part;              // granule workspace (null: no split) ...
     size_t ks_part_bytes;        // ... and its size
@@ -102,8 +102,9 @@ struct SkinnyParams {
 };
 constexpr int SKINNY_W_FP8 = 1;
 void launch_skinny(const SkinnyParams& p, bool bf16, hipStream_t st);
-// the kernel family the calling thread's last launch_skinny ran: skinny2_kernel | skinny8_kernel (| SKINNY_KERNEL_FP8: their fp8 forms), or another
-enum { SKINNY_KERNEL_OTHER = 0, SKINNY_KERNEL_2 = 2, SKINNY_KERNEL_8 = 8, SKINNY_KERNEL_FP8 = 16 };
+// the kernel family the calling thread's last launch_skinny ran: skinny2_kernel | skinny2_ks_kernel (split-K) | skinny8_kernel
+// (| SKINNY_KERNEL_FP8: their fp8 forms), or another
+enum { SKINNY_KERNEL_OTHER = 0, SKINNY_KERNEL_2 = 2, SKINNY_KERNEL_KS = 4, SKINNY_KERNEL_8 = 8, SKINNY_KERNEL_FP8 = 16 };
 int skinny_last_kernel();
 void skinny_set_launch_events(hipEvent_t start, hipEvent_t stop);   // (bench.py's roofline leg: time the NEXT launch on its own; null = off)
 constexpr int SKINNY_MAX_ROWS = 128;                 // 65..128 rows: skinny_wide_kernel / the fp32 kernel's 8-tile form (pass 0 of the code predictor at batch 33..64)

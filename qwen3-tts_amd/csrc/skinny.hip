@@ -543,7 +543,7 @@ __global__ __launch_bounds__(NW * 64) void skinny_wide_kernel(SkinnyParams p) {
     }
 }
 
-// ------------------------------------------------------------------------------------------ bf16, batch 17..32, deep K: split-K (round 6)
+// ------------------------------------------------------------------------------------------ bf16 / fp8 weights, batch 17..32, deep K: split-K (round 6)
 // At batch 17..32 (two 16-row tiles of x) a workgroup of skinny2_kernel pulls M x K x 2 B of x whatever its strip width: the talker's
 // down-projection (K = 6144, 256 workgroups of ONE 8-feature strip) moves 393 KB of x against 98 KB of weights per workgroup -- 100 MB
 // of L2 -> CU traffic for a 25 MB operator, 14.5 us per launch against 5.7 us at batch 8 (profiles/r03_skinny_b32_straight.md).  The x
@@ -577,9 +577,17 @@ __global__ __launch_bounds__(NW * 64) void skinny_wide_kernel(SkinnyParams p) {
 #else
 #define QTTS_KS_TS_END(red_) do { } while (0)
 #endif
-template <int SPW, int FS, int NW, int TPW, int KS>
-__global__ __launch_bounds__(NW * 64) void skinny2_ks_kernel(SkinnyParams p) {
+// W8 (fp8 weights, opt-in; skinny2_ks_fp8_kernel below shares this body): a weight request is 8 B of e4m3fn codes per lane under the same
+// exec mask -- the same (ks, wave, i) -> k-tile deal, addressed as skinny2_body addresses its codes (fs = 8: the bf16 index in 8-byte
+// units; fs = 16: half kt & 1 of tile pair kt >> 1) -- converted right in front of its MFMA.  Granules carry the UNSCALED sums of
+// code x x; the reducer multiplies the k-ordered total by the row's power-of-two scale (requested with the residual and the bias) and
+// then adds bias and residual: a power of two commutes with every fp32 rounding of the chain, so the rows are the bf16 kernel's on
+// d = code x 2^e bit for bit.
+template <int SPW, int FS, int NW, int TPW, int KS, bool W8>
+__device__ __forceinline__ void skinny2_ks_body(SkinnyParams& p) {
+    typedef typename SkinnyWReg<W8>::type wreg;
     constexpr int MT = 2, KT = 32, NP = SPW * MT, PPW = (NP + NW - 1) / NW;
+    constexpr bool WPAIR = W8 && FS == 16;                       // fp8, 16-feature strips: tile pairs, 16 B per (k-slice, feature)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_sk[];
     f32x4* red = reinterpret_cast<f32x4*>(smem_sk);             // [NW][NP][64]
     QTTS_TS_BEGIN();
@@ -593,11 +601,12 @@ __global__ __launch_bounds__(NW * 64) void skinny2_ks_kernel(SkinnyParams p) {
     const bool wlane = lj < FS;
     const bool reducer = ks == KS - 1;
 
-    u32x4 wR[TPW][SPW], xR[TPW][MT];
+    wreg wR[TPW][SPW];
+    u32x4 xR[TPW][MT];
 #pragma unroll
     for (int i = 0; i < TPW; ++i) {
 #pragma unroll
-        for (int s = 0; s < SPW; ++s) wR[i][s] = (u32x4){0u, 0u, 0u, 0u};
+        for (int s = 0; s < SPW; ++s) wR[i][s] = wreg{};
 #pragma unroll
         for (int m = 0; m < MT; ++m) xR[i][m] = (u32x4){0u, 0u, 0u, 0u};
     }
@@ -605,8 +614,11 @@ __global__ __launch_bounds__(NW * 64) void skinny2_ks_kernel(SkinnyParams p) {
 #pragma unroll
         for (int i = 0; i < TPW; ++i)
 #pragma unroll
-            for (int s = 0; s < SPW; ++s)
-                wR[i][s] = skinny_wload(reinterpret_cast<const u32x4*>(p.Wp) + ((size_t)(strip0 + s) * nkt + kt0 + NW * i) * (FS * 4) + lq * FS + (wlane ? lj : 0));
+            for (int s = 0; s < SPW; ++s) {
+                const int kt = kt0 + NW * i;
+                if constexpr (WPAIR) wR[i][s] = skinny_wload(reinterpret_cast<const wreg*>(p.Wp) + (((size_t)(strip0 + s) * ((nkt + 1) >> 1) + (kt >> 1)) * 64 + lq * 16 + lj) * 2 + (kt & 1));
+                else wR[i][s] = skinny_wload(reinterpret_cast<const wreg*>(p.Wp) + ((size_t)(strip0 + s) * nkt + kt) * (FS * 4) + lq * FS + (wlane ? lj : 0));
+            }
     }
 #pragma unroll
     for (int m = 0; m < MT; ++m)
@@ -616,15 +628,17 @@ __global__ __launch_bounds__(NW * 64) void skinny2_ks_kernel(SkinnyParams p) {
             for (int i = 0; i < TPW; ++i) xR[i][m] = *reinterpret_cast<const u32x4*>(xp + (size_t)(kt0 + NW * i) * KT);
         }
     // the reducer's epilogue operands, under the weight stream
-    f32x4 resv[PPW], biasv[PPW];
+    f32x4 resv[PPW], biasv[PPW], scv[W8 ? PPW : 1];
 #pragma unroll
     for (int j = 0; j < PPW; ++j) {
         resv[j] = (f32x4){0.f, 0.f, 0.f, 0.f}; biasv[j] = resv[j];
+        if constexpr (W8) scv[j] = (f32x4){1.f, 1.f, 1.f, 1.f};
         const int pr = wave + NW * j, s = pr / MT, m = pr - s * MT;
         const int row = m * 16 + lj, col = (strip0 + s) * FS + lq * 4;
         if (reducer && pr < NP && row < p.M && lq * 4 < FS) {
             if (p.res) resv[j] = *reinterpret_cast<const f32x4*>(p.res + (size_t)row * p.ldr + col);
             if (p.bias) biasv[j] = *reinterpret_cast<const f32x4*>(p.bias + col);
+            if constexpr (W8) scv[j] = *reinterpret_cast<const f32x4*>(p.wscale + col);      // the rows' power-of-two scales
         }
     }
     const unsigned serial = p.ks_serial ? (unsigned)*p.ks_serial : 1u;
@@ -640,7 +654,10 @@ __global__ __launch_bounds__(NW * 64) void skinny2_ks_kernel(SkinnyParams p) {
 #pragma unroll
         for (int m = 0; m < MT; ++m) acc[s][m] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int i = 0; i < TPW; ++i)
+    for (int i = 0; i < TPW; ++i) {
+        u32x4 wv[SPW];                                           // (fp8: converted once per tile, in front of its MFMAs)
+#pragma unroll
+        for (int s = 0; s < SPW; ++s) wv[s] = skinny_wa(wR[i][s]);
 #pragma unroll
         for (int m = 0; m < MT; ++m) {
             bf16x8 xb;
@@ -648,10 +665,11 @@ __global__ __launch_bounds__(NW * 64) void skinny2_ks_kernel(SkinnyParams p) {
 #pragma unroll
             for (int s = 0; s < SPW; ++s) {
                 bf16x8 wa;
-                *reinterpret_cast<u32x4*>(&wa) = wR[i][s];
+                *reinterpret_cast<u32x4*>(&wa) = wv[s];
                 acc[s][m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa, xb, acc[s][m], 0, 0, 0);
             }
         }
+    }
 #pragma unroll
     for (int s = 0; s < SPW; ++s)
 #pragma unroll
@@ -729,10 +747,19 @@ __global__ __launch_bounds__(NW * 64) void skinny2_ks_kernel(SkinnyParams p) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) t[r] += __uint_as_float(g[j][k2][r >> 1][(r & 1) * 2]);
         t += own[j];
+        if constexpr (W8) t = t * scv[j];                        // 2^e[n]: exact, and what the bf16 kernel's sums over d are
         skinny_store4(p, row, col, t + biasv[j] + resv[j], true);
     }
     QTTS_TS_DRAINED(5);
     QTTS_KS_TS_END(1);
+}
+template <int SPW, int FS, int NW, int TPW, int KS>
+__global__ __launch_bounds__(NW * 64) void skinny2_ks_kernel(SkinnyParams p) {
+    skinny2_ks_body<SPW, FS, NW, TPW, KS, false>(p);
+}
+template <int SPW, int FS, int NW, int TPW, int KS>
+__global__ __launch_bounds__(NW * 64) void skinny2_ks_fp8_kernel(SkinnyParams p) {
+    skinny2_ks_body<SPW, FS, NW, TPW, KS, true>(p);
 }
 
 // ------------------------------------------------------------------------------------------ bf16, batch <= 8 (the benchmarked shape)
@@ -1391,6 +1418,7 @@ static void launch_skinny_halves(const SkinnyParams& p, bool bf16, hipStream_t s
 // QTTS_SKINNY_KS_MINK: the smallest K that splits.  Default 6144 -- the talker's down-projection only: 14.65 -> 10.7 us per launch, frame step at
 // batch 32 4.46 -> 4.31 ms (-3.4 %).  At K = 3072 (the 1024-wide stacks' down-projection, 8 parts) the combine costs what the split saves
 // (8.36 -> 8.9 us per launch: 4.39 ms), at K = 2048 it loses (4.55 ms): in-process A/B and timelines in profiles/r06_skinny_ksplit.md.
+// fp8 weights (p.wfmt) take the W8 instantiation of the same four shapes under the same switches (profiles/fp8_weights.md).
 static int ksplit_choice(int M, int N, int K, int fs) {
     if (M <= 16 || M > 32 || N % 32 != 0 || K % 32 != 0) return 0;
     const int groups = N / 32, nkt = K / 32, ks = groups >= 64 ? 4 : 8;
@@ -1407,8 +1435,11 @@ static void launch_ks_n(const SkinnyParams& p, hipStream_t st) {
     const size_t lds = (size_t)NW * SPW * 2 * 64 * 16;
     QTTS_REQUIRE((size_t)grid * SPW * 2 * 64 * 32 <= p.ks_part_bytes, QTTS_ERR_LIMIT, "skinny: the split-K workspace is too small for this launch");
     QTTS_REQUIRE(p.ks_slot >= 0 && p.ks_slot < 256, QTTS_ERR_ARG, "skinny: split-K launch slot must be < 256");
-    auto kern = skinny2_ks_kernel<SPW, FS, NW, TPW, KS>;
+    const bool w8 = p.wfmt == SKINNY_W_FP8;
+    QTTS_REQUIRE(!w8 || p.wscale, QTTS_ERR_ARG, "skinny: fp8 weights need their row scales");
+    auto kern = w8 ? skinny2_ks_fp8_kernel<SPW, FS, NW, TPW, KS> : skinny2_ks_kernel<SPW, FS, NW, TPW, KS>;
     if (lds > 48 * 1024) ensure_dynamic_lds(reinterpret_cast<const void*>(kern), 160 * 1024);
+    tl_last_kernel = SKINNY_KERNEL_KS | (w8 ? SKINNY_KERNEL_FP8 : 0);
     QTTS_SK_LAUNCH(kern, dim3(grid), dim3(NW * 64), lds, st, p);
 }
 static bool launch_skinny_ks(const SkinnyParams& p, int fs, hipStream_t st) {
@@ -1599,11 +1630,11 @@ void launch_skinny(const SkinnyParams& p, bool bf16, hipStream_t st) {
     QTTS_REQUIRE(!p.out_bf16 || bf16, QTTS_ERR_ARG, "skinny: bf16 output only in bf16 mode");
     QTTS_REQUIRE(bf16 || !p.norm || p.ss_in || skinny_f32_inline_norm(p.M, p.K), QTTS_ERR_ARG,
                  "skinny: the generic fp32 kernel takes the row sums of squares from ss_in");
-    if (p.wfmt) {                        // fp8 weights: skinny8_fp8_kernel (batch <= 8, K % 512 == 0), else skinny2_fp8_kernel; no other kernel reads codes
+    if (p.wfmt) {                        // fp8 weights: skinny8_fp8_kernel (batch <= 8, K % 512 == 0), skinny2_ks_fp8_kernel (batch 17..32, split shapes), else skinny2_fp8_kernel; no other kernel reads codes
         QTTS_REQUIRE(p.wfmt == SKINNY_W_FP8, QTTS_ERR_ARG, "skinny: unknown weight format");
         QTTS_REQUIRE(bf16 && p.x_bf16, QTTS_ERR_ARG, "skinny: fp8 weights need the bf16 kernel and x as bf16 rows");
         QTTS_REQUIRE(p.M <= 64, QTTS_ERR_LIMIT, "skinny: fp8 weights are built for M <= 64");
-        QTTS_REQUIRE(p.wscale && !p.ksplit && !p.xp && !p.ks_part && !QTTS_ABL(p, 15), QTTS_ERR_ARG, "skinny: fp8 weights need their row scales and take no split-K / combine / ablation form");
+        QTTS_REQUIRE(p.wscale && !p.ksplit && !p.xp && !QTTS_ABL(p, 15), QTTS_ERR_ARG, "skinny: fp8 weights need their row scales and take no fp32 split-K / combine / ablation form");
     }
     if (p.act == ACT_SWIGLU) QTTS_REQUIRE(p.N % 32 == 0 && fs == 16, QTTS_ERR_ARG, "skinny: swiglu needs N % 32 and fs == 16");
     if (p.act == ACT_SWIGLU8) {          // one 16-feature strip = 8 gate + 8 up rows: only the batch <= 8 kernel has this epilogue
@@ -1626,7 +1657,7 @@ void launch_skinny(const SkinnyParams& p, bool bf16, hipStream_t st) {
     }
     const int mt = p.M <= 16 ? 1 : (p.M <= 32 ? 2 : 4);
     if (bf16 && nw == 8 && mt == 1 && launch_skinny8(p, spw, fs, st)) { QTTS_CHECK_HIP(hipGetLastError()); return; }
-    if (bf16 && mt == 2 && !p.wfmt && launch_skinny_ks(p, fs, st)) { QTTS_CHECK_HIP(hipGetLastError()); return; }
+    if (bf16 && mt == 2 && launch_skinny_ks(p, fs, st)) { QTTS_CHECK_HIP(hipGetLastError()); return; }
     if (!bf16 && !QTTS_ABL(p, 15) && launch_skinny8_f32(p, spw, st)) { QTTS_CHECK_HIP(hipGetLastError()); return; }
     if (bf16) {
         if (nw == 8) { if (mt == 1) launch2_mt<1, 8>(p, spw, fs, st); else if (mt == 2) launch2_mt<2, 8>(p, spw, fs, st); else launch2_mt<4, 8>(p, spw, fs, st); }

@@ -437,8 +437,11 @@ struct qtts_talker {
     int64_t ks_split_count = 0;
     int ks_split_per_step = 0;
     int ks_mink = QTTS_OPT_INT("QTTS_SKINNY_KS_MINK", 6144);
+    // fp8 operators split the same shapes on skinny2_ks_fp8_kernel (same workspace, slots and serial).  QTTS_SKINNY_KS_FP8=0 (copied at engine
+    // creation, consulted here only): an fp8 operator keeps skinny2_fp8_kernel -- the in-process A/B of tools/bench_fp8.py.
+    bool ks_fp8_env = QTTS_OPT_ON("QTTS_SKINNY_KS_FP8");
     void ks_arm(SkinnyParams& q, int slot) {
-        if (q.wfmt) return;                // (an fp8 operator keeps skinny2_fp8_kernel: the split-K kernel reads bf16 tiles)
+        if (q.wfmt && !ks_fp8_env) return;
         if (!ks_split_env || !ks_part.p || !bf16 || q.M <= 16 || q.M > 32 || slot < 0 || slot >= 256 || skinny_only) return;
         if (q.K < ks_mink || !skinny_ksplit_takes(q.M, q.N, q.K, q.fs ? q.fs : 16)) return;
         q.ks_part = ks_part.as<float>(); q.ks_part_bytes = ks_part.bytes; q.ks_serial = ss.frame_serial; q.ks_slot = slot; q.ks_pause = ks_pause;
@@ -2160,21 +2163,15 @@ int qtts_debug_last_decode_gemm_kernel(int32_t* kind_host) {
     QTTS_API_END
 }
 
-// TEST HOOK: one launch_skinny call on host operands, bf16 or fp8 weights (include/qtts.h)
-int qtts_debug_decode_gemm(const float* x, const float* W, const float* g_or_null, const float* bias_or_null, const float* res_or_null,
-                           int32_t M, int32_t N, int32_t K, int32_t fs, int32_t norm, int32_t act, int32_t fmt, int32_t ldo,
-                           float* out, uint16_t* out16_or_null) {
-    QTTS_API_BEGIN
-    QTTS_REQUIRE(x && W && out, QTTS_ERR_ARG, "debug_decode_gemm: null argument");
-    QTTS_REQUIRE(M >= 1 && M <= 64 && N >= 16 && K >= 32 && K % 32 == 0, QTTS_ERR_ARG, "debug_decode_gemm: 1 <= M <= 64, N >= 16, K % 32 == 0");
-    QTTS_REQUIRE(fs == 16 || fs == 8 || fs == 4, QTTS_ERR_ARG, "debug_decode_gemm: fs must be 16, 8 or 4");
-    QTTS_REQUIRE(N % fs == 0, QTTS_ERR_ARG, "debug_decode_gemm: N % fs");
-    QTTS_REQUIRE(fmt == QTTS_WEIGHTS_DEFAULT || fmt == QTTS_WEIGHTS_FP8, QTTS_ERR_ARG, "debug_decode_gemm: unknown weight format");
-    const bool glu = act == ACT_SWIGLU || act == ACT_SWIGLU8;
-    QTTS_REQUIRE(act == ACT_NONE || glu, QTTS_ERR_ARG, "debug_decode_gemm: act 0, 2 (SwiGLU strip pairs) or 5 (SwiGLU of one strip)");
-    const int No = glu ? N / 2 : N;
-    QTTS_REQUIRE(ldo >= No && ldo % 4 == 0, QTTS_ERR_ARG, "debug_decode_gemm: ldo >= output columns, ldo % 4 == 0");
-    DevBuf Wd, sd, xd, od, o16d, rd, bd;
+// TEST HOOKS: launch_skinny on host operands, bf16 or fp8 weights (include/qtts.h).  `launches` > 0: the split-K form's operands as well --
+// an 8 MB granule workspace of 0xFF, a device serial word, device err / latch words -- and that many launches on the one workspace
+// (slots 3 + 7 l); out / out16 then carry a guard row behind row M.
+static void debug_decode_gemm(const float* x, const float* W, const float* g_or_null, const float* bias_or_null, const float* res_or_null,
+                              int32_t M, int32_t N, int32_t K, int32_t fs, int32_t norm, int32_t act, int32_t fmt, int32_t ldo,
+                              float* out, uint16_t* out16_or_null, int32_t launches, int32_t serial) {
+    const bool ks = launches > 0;
+    const size_t orows = (size_t)M + (ks ? 1 : 0);
+    DevBuf Wd, sd, xd, od, o16d, rd, bd, partd, wordsd;
     if (fmt == QTTS_WEIGHTS_FP8) {
         std::vector<char> h(skinny_fp8_code_bytes(N, K, fs));
         std::vector<float> s((size_t)N);
@@ -2189,8 +2186,8 @@ int qtts_debug_decode_gemm(const float* x, const float* W, const float* g_or_nul
     std::vector<bf16_t> x16((size_t)M * K);
     for (size_t i = 0; i < x16.size(); ++i) x16[i] = f32_to_bf16(x[i]);
     xd.upload(x16.data(), x16.size() * 2);
-    od.upload(out, (size_t)M * ldo * 4);
-    if (out16_or_null) o16d.upload(out16_or_null, (size_t)M * ldo * 2);
+    od.upload(out, orows * ldo * 4);
+    if (out16_or_null) o16d.upload(out16_or_null, orows * ldo * 2);
     if (res_or_null) rd.upload(res_or_null, (size_t)M * ldo * 4);
     if (bias_or_null) bd.upload(bias_or_null, (size_t)N * 4);
     SkinnyParams p{};
@@ -2199,10 +2196,57 @@ int qtts_debug_decode_gemm(const float* x, const float* W, const float* g_or_nul
     if (res_or_null) { p.res = rd.as<float>(); p.ldr = ldo; }
     p.out = od.as<float>(); p.ldo = ldo; p.out16 = out16_or_null ? o16d.p : nullptr; p.act = act;
     if (fmt == QTTS_WEIGHTS_FP8) { p.wfmt = SKINNY_W_FP8; p.wscale = sd.as<float>(); }
-    launch_skinny(p, true, nullptr);
+    int32_t words[3] = {serial, 0, 0};                          // serial, err, latch
+    if (ks) {
+        partd.alloc((size_t)8 << 20);
+        QTTS_CHECK_HIP(hipMemset(partd.p, 0xFF, partd.bytes));
+        wordsd.upload(words, sizeof(words));
+        p.ks_part = partd.as<float>(); p.ks_part_bytes = partd.bytes; p.ks_serial = wordsd.as<int>(); p.ks_pause = 8;
+        p.ks_err = wordsd.as<int>() + 1; p.ks_latch = wordsd.as<int>() + 2;
+    }
+    for (int l = 0; l < (ks ? launches : 1); ++l) {
+        if (ks) p.ks_slot = 3 + 7 * l;
+        launch_skinny(p, true, nullptr);
+    }
     QTTS_CHECK_HIP(hipDeviceSynchronize());
-    QTTS_CHECK_HIP(hipMemcpy(out, od.p, (size_t)M * ldo * 4, hipMemcpyDeviceToHost));
-    if (out16_or_null) QTTS_CHECK_HIP(hipMemcpy(out16_or_null, o16d.p, (size_t)M * ldo * 2, hipMemcpyDeviceToHost));
+    QTTS_CHECK_HIP(hipMemcpy(out, od.p, orows * ldo * 4, hipMemcpyDeviceToHost));
+    if (out16_or_null) QTTS_CHECK_HIP(hipMemcpy(out16_or_null, o16d.p, orows * ldo * 2, hipMemcpyDeviceToHost));
+    if (ks) {
+        QTTS_CHECK_HIP(hipMemcpy(words, wordsd.p, sizeof(words), hipMemcpyDeviceToHost));
+        QTTS_REQUIRE(words[1] == 0 && words[2] == 0, QTTS_ERR_STATE, "debug_decode_gemm_ks: a reducer gave up waiting for its strip group's partial sums");
+    }
+}
+
+int qtts_debug_decode_gemm(const float* x, const float* W, const float* g_or_null, const float* bias_or_null, const float* res_or_null,
+                           int32_t M, int32_t N, int32_t K, int32_t fs, int32_t norm, int32_t act, int32_t fmt, int32_t ldo,
+                           float* out, uint16_t* out16_or_null) {
+    QTTS_API_BEGIN
+    QTTS_REQUIRE(x && W && out, QTTS_ERR_ARG, "debug_decode_gemm: null argument");
+    QTTS_REQUIRE(M >= 1 && M <= 64 && N >= 16 && K >= 32 && K % 32 == 0, QTTS_ERR_ARG, "debug_decode_gemm: 1 <= M <= 64, N >= 16, K % 32 == 0");
+    QTTS_REQUIRE(fs == 16 || fs == 8 || fs == 4, QTTS_ERR_ARG, "debug_decode_gemm: fs must be 16, 8 or 4");
+    QTTS_REQUIRE(N % fs == 0, QTTS_ERR_ARG, "debug_decode_gemm: N % fs");
+    QTTS_REQUIRE(fmt == QTTS_WEIGHTS_DEFAULT || fmt == QTTS_WEIGHTS_FP8, QTTS_ERR_ARG, "debug_decode_gemm: unknown weight format");
+    const bool glu = act == ACT_SWIGLU || act == ACT_SWIGLU8;
+    QTTS_REQUIRE(act == ACT_NONE || glu, QTTS_ERR_ARG, "debug_decode_gemm: act 0, 2 (SwiGLU strip pairs) or 5 (SwiGLU of one strip)");
+    const int No = glu ? N / 2 : N;
+    QTTS_REQUIRE(ldo >= No && ldo % 4 == 0, QTTS_ERR_ARG, "debug_decode_gemm: ldo >= output columns, ldo % 4 == 0");
+    debug_decode_gemm(x, W, g_or_null, bias_or_null, res_or_null, M, N, K, fs, norm, act, fmt, ldo, out, out16_or_null, 0, 0);
+    QTTS_API_END
+}
+
+int qtts_debug_decode_gemm_ks(const float* x, const float* W, const float* g_or_null, const float* bias_or_null, const float* res_or_null,
+                              int32_t M, int32_t N, int32_t K, int32_t fs, int32_t fmt, int32_t ldo, float* out, uint16_t* out16_or_null,
+                              int32_t launches, int32_t serial) {
+    QTTS_API_BEGIN
+    QTTS_REQUIRE(x && W && out, QTTS_ERR_ARG, "debug_decode_gemm_ks: null argument");
+    QTTS_REQUIRE(M >= 1 && M <= 64 && N >= 16 && K >= 32 && K % 32 == 0, QTTS_ERR_ARG, "debug_decode_gemm_ks: 1 <= M <= 64, N >= 16, K % 32 == 0");
+    QTTS_REQUIRE(fs == 16 || fs == 8 || fs == 4, QTTS_ERR_ARG, "debug_decode_gemm_ks: fs must be 16, 8 or 4");
+    QTTS_REQUIRE(N % fs == 0, QTTS_ERR_ARG, "debug_decode_gemm_ks: N % fs");
+    QTTS_REQUIRE(fmt == QTTS_WEIGHTS_DEFAULT || fmt == QTTS_WEIGHTS_FP8, QTTS_ERR_ARG, "debug_decode_gemm_ks: unknown weight format");
+    QTTS_REQUIRE(ldo >= N && ldo % 4 == 0, QTTS_ERR_ARG, "debug_decode_gemm_ks: ldo >= output columns, ldo % 4 == 0");
+    QTTS_REQUIRE(launches >= 1 && launches <= 36, QTTS_ERR_ARG, "debug_decode_gemm_ks: 1 <= launches <= 36 (slots 3 + 7 l < 256)");
+    QTTS_REQUIRE(serial >= 1 && serial < (1 << 23), QTTS_ERR_ARG, "debug_decode_gemm_ks: 1 <= serial < 2^23");
+    debug_decode_gemm(x, W, g_or_null, bias_or_null, res_or_null, M, N, K, fs, 0, ACT_NONE, fmt, ldo, out, out16_or_null, launches, serial);
     QTTS_API_END
 }
 
